@@ -23,7 +23,17 @@ is restored to the cold start each time; the path is deterministic, so
 every episode runs the identical iteration count).
 
 Contract (driver-run):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+  A plain run does only what the headline figure needs: set up, warm
+  up, time exactly K episodes, print one JSON result line.
+  --dump-outputs DIR writes, after the timed episodes, what the last
+  timed episode computed as float64 DIR/<name>.npy (see dump_outputs).
+  The inputs are the shipped dataset and a deterministic initial state,
+  so two builds run with the same arguments can be compared output for
+  output.
+  --full is reserved for measurements beyond the headline figure (CPU
+  baselines, other configurations, per-kernel figures). This benchmark
+  has none of its own, so today --full runs the same as a plain run.
   For N > 1 the driver launches this under torch.distributed.run with
   one rank per GPU (RCCL over xGMI); rank/world read from the env.
   The 8 agents are spread over ranks; total work is fixed => strong
@@ -44,6 +54,35 @@ import sys
 import time
 
 
+def dump_outputs(out_dir, drv, res, rank) -> None:
+    """Write what the last timed episode returned to its caller:
+      trace.npy       (iterations, 2)  per-round [cost, gradnorm] of the
+                                       returned RBCDResult
+      X.npy           (n, d+1, r)      the lifted iterate the driver is
+                                       left holding, in global pose order
+      trajectory.npy  (d, (d+1) n)     the rounded global trajectory
+    All float64 and whole (sphere2500: about 0.7 MB in total). The two
+    gathers are collectives, so every rank takes part; rank 0 writes."""
+    import numpy as np
+    import torch
+
+    X = torch.zeros(drv.n_global, drv.dh, drv.r, dtype=torch.float64)
+    for rb, a in drv.local_agents.items():
+        gidx = torch.tensor([drv.pose_to_index[(rb, i)]
+                             for i in range(a.n)], dtype=torch.long)
+        X[gidx] = a.X.detach().cpu().reshape(a.n, drv.dh, drv.r)
+    drv.comm.all_reduce_sum_(X.view(-1))
+    T = drv.gather_final_trajectory()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "trace.npy"),
+            np.asarray(res.trace, dtype=np.float64).reshape(-1, 2))
+    np.save(os.path.join(out_dir, "X.npy"), X.numpy())
+    np.save(os.path.join(out_dir, "trajectory.npy"),
+            np.asarray(T, dtype=np.float64))
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -57,7 +96,16 @@ def main() -> int:
     ap.add_argument("--selection", type=str, default="colored")
     ap.add_argument("--partition", type=str, default="contiguous")
     ap.add_argument("--tol", type=float, default=0.1)
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the last timed episode's outputs as "
+                         "DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run measurements beyond the headline "
+                         "figure (this benchmark has none: same as a "
+                         "plain run)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -124,6 +172,10 @@ def main() -> int:
         elapsed = float(tt.item())
 
     per_episode = elapsed / args.steps
+
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, drv, res, rank)
+
     if rank == 0:
         out = {
             "metric": f"{args.dataset}_wall_to_gradnorm_0.1_s",

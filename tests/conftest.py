@@ -5,8 +5,6 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-REFERENCE_DATA = "/root/reference/data"
-
 
 def pytest_configure(config):
     config.addinivalue_line(
@@ -21,10 +19,3 @@ def pytest_collection_modifyitems(config, items):
     for item in items:
         if "gpu" in item.keywords:
             item.add_marker(skip)
-
-
-@pytest.fixture
-def reference_data_dir():
-    if not os.path.isdir(REFERENCE_DATA):
-        pytest.skip("reference datasets not available on this box")
-    return REFERENCE_DATA

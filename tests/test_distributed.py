@@ -94,7 +94,9 @@ def test_world4_accel_colored_combined_payload():
 def test_bench_torchrun_world2_cpu():
     """bench.py under torch.distributed.run with 2 ranks (gloo, CPU):
     the exact launch path the driver's multi-GPU SCALE run uses. The
-    episode must converge with the same iteration count as world=1."""
+    episode must converge with the same iteration count as world=1.
+    Pinned to --device cpu so both ranks take the gloo path on any
+    machine, including one with fewer than 2 GPUs."""
     import subprocess
     import sys
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -103,7 +105,7 @@ def test_bench_torchrun_world2_cpu():
          "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29787", "bench.py", "--gpus", "2",
          "--steps", "2", "--warmup", "1", "--dataset", "smallGrid3D",
-         "--agents", "4"],
+         "--agents", "4", "--device", "cpu"],
         capture_output=True, text=True, timeout=600, cwd=here)
     assert out.returncode == 0, out.stderr[-2000:]
     o = json.loads(out.stdout.strip().splitlines()[-1])

@@ -1,14 +1,12 @@
 """Multi-robot RBCD driver tests: convergence on synthetic graphs, robust
 GNC outlier rejection, acceleration, partitioning, g2o round-trip, and
-(when the reference checkout is present) end-to-end trace parity."""
-import os
-
+end-to-end trace parity with the reference on the shipped datasets."""
 import numpy as np
 import pytest
 
 from dpo_amd.driver import MultiRobotDriver
-from dpo_amd.io_g2o import (adjacency_from_measurements, read_g2o,
-                            read_partition_file, write_g2o)
+from dpo_amd.io_g2o import (adjacency_from_measurements, load_dataset,
+                            read_g2o, read_partition_file, write_g2o)
 from dpo_amd.partition import (contiguous_partition, cut_edges,
                                multilevel_partition)
 from dpo_amd.synthetic import city2d, grid3d, sphere
@@ -119,10 +117,11 @@ def test_g2o_roundtrip(tmp_path):
         assert abs(a.tau - b.tau) < 1e-4 * a.tau
 
 
-def test_reference_csail_parity(reference_data_dir):
+def test_reference_csail_parity():
     """End-to-end parity vs the recorded reference trace: iterations to
-    centralized gradnorm < 0.1 within ~5%, final cost within 1e-3."""
-    meas, n = read_g2o(os.path.join(reference_data_dir, "CSAIL.g2o"))
+    centralized gradnorm < 0.1 within ~5%, final cost within 1e-3.
+    Runs on the shipped data/CSAIL.npz (same measurements as the .g2o)."""
+    meas, n = load_dataset("CSAIL")
     drv = MultiRobotDriver(meas, n, 5, r=5, partition="contiguous")
     res = drv.run(max_iters=1000)
     assert res.converged
@@ -130,8 +129,8 @@ def test_reference_csail_parity(reference_data_dir):
     assert abs(res.final_cost - 31.47) < 0.01
 
 
-def test_reference_parking_garage_parity(reference_data_dir):
-    meas, n = read_g2o(os.path.join(reference_data_dir, "parking-garage.g2o"))
+def test_reference_parking_garage_parity():
+    meas, n = load_dataset("parking-garage")
     drv = MultiRobotDriver(meas, n, 5, r=5, partition="contiguous")
     res = drv.run(max_iters=1000)
     assert res.converged
