@@ -32,11 +32,11 @@
 #include <stdlib.h>
 #include <string.h>
 
-// Debug/bisection knobs: DPO_NO_SOLVE_GRAPH=1 / DPO_NO_EVAL_GRAPH=1 run
-// the solve / eval sequences eagerly instead of via cached hipGraphs.
 // teardown/cleanup calls whose errors are deliberately ignored
 static inline void dpo_ignore(hipError_t) {}
 
+// Debug/bisection knobs: DPO_NO_SOLVE_GRAPH=1 / DPO_NO_EVAL_GRAPH=1 run
+// the solve / eval sequences eagerly instead of via cached hipGraphs.
 static bool dpo_env_flag(const char* name) {
   const char* v = getenv(name);
   return v && v[0] == '1';
@@ -135,12 +135,16 @@ __device__ __forceinline__ bool fanin_last_block(double* ctrl) {
   return is_last != 0;
 }
 
-// Control tails (single thread of the last block). Mirror the k_ctrl_*
-// kernels; dot slots are read L2-coherently, results stored L2-visibly
-// (the next kernel's dispatch acquire makes them visible to all CUs).
+// Control tails: the tCG scalar decisions, run by a single thread —
+// thread 0 of the last-arriving block of the producing reduction kernel
+// (fused, the default) or of a standalone k_ctrl_tail launch
+// (DPO_NO_CF=1). Dot slots are read L2-coherently, results stored
+// L2-visibly (the next kernel's dispatch acquire makes them visible to
+// all CUs).
 enum CtrlFuse { CF_NONE = 0, CF_Z0 = 1, CF_ALPHA = 2, CF_RR = 3,
                 CF_BETA = 4, CF_COMBINE = 5 };
 
+// after z0 projection+dot (C_DOT0 = <z0, r0>)
 __device__ void ctrl_tail_z0(double* ctrl) {
   if (ctrl[C_STATUS] != (double)ST_RUN) return;
   const double zr = ctrl_load(ctrl + C_DOT0);
@@ -149,6 +153,7 @@ __device__ void ctrl_tail_z0(double* ctrl) {
   ctrl_store(ctrl + C_DOT0, 0.0);
 }
 
+// after Hd projection+dot (C_DOT0 = <delta, Hd>): alpha / boundary logic
 __device__ void ctrl_tail_alpha(double* ctrl) {
   if (ctrl[C_STATUS] != (double)ST_RUN) return;
   const int j = (int)ctrl[C_ITER];
@@ -157,6 +162,7 @@ __device__ void ctrl_tail_alpha(double* ctrl) {
   const double z_r = ctrl[C_ZR];
   const double e_Pe = ctrl[C_EPE], e_Pd = ctrl[C_EPD], d_Pd = ctrl[C_DPD];
   const double radius = ctrl[C_RADIUS];
+  // scalar history for radius-replay (shrink loop reuses the Krylov path)
   ctrl_store(ctrl + H_ZR(j), z_r);
   ctrl_store(ctrl + H_DHD(j), d_Hd);
   ctrl_store(ctrl + H_EPE(j), e_Pe);
@@ -177,12 +183,13 @@ __device__ void ctrl_tail_alpha(double* ctrl) {
   }
 }
 
+// after k_tcg_update (C_DOT1 = ||r||^2 when continuing)
 __device__ void ctrl_tail_rr(double* ctrl) {
   if (ctrl[C_STATUS] != (double)ST_RUN) return;
   const int j = (int)ctrl[C_ITER];
   if (ctrl[C_STOP_PENDING] != 0.0) {
     ctrl_store(ctrl + C_STATUS, (double)ST_TCG_STOP);
-    ctrl_store(ctrl + C_J, (double)j);
+    ctrl_store(ctrl + C_J, (double)j);  // truncated at snapshot j
     ctrl_store(ctrl + C_HLEN, (double)(j + 1));
     ctrl_store(ctrl + C_USE_CURRENT, 0.0);
     return;
@@ -194,10 +201,12 @@ __device__ void ctrl_tail_rr(double* ctrl) {
     ctrl_store(ctrl + C_STATUS, (double)ST_TCG_STOP);
     ctrl_store(ctrl + C_J, (double)(j + 1));
     ctrl_store(ctrl + C_HLEN, (double)(j + 1));
+    // converged: step = current eta
     ctrl_store(ctrl + C_USE_CURRENT, 1.0);
   }
 }
 
+// after z projection+dot (C_DOT0 = <z, r>): beta and delta scalars
 __device__ void ctrl_tail_beta(double* ctrl) {
   if (ctrl[C_STATUS] != (double)ST_RUN) return;
   const double z_r_new = ctrl_load(ctrl + C_DOT0);
@@ -1194,657 +1203,6 @@ __global__ void k_dots(const double* __restrict__ A,
 }
 
 // ---------------------------------------------------------------------
-// Persistent solve kernel: the ENTIRE pre-sync local solve — G
-// assembly, gradient phase, z0, the Steihaug tCG loop, the first
-// candidate (replay + polar retraction + f evaluation) and the
-// acceptance test — as ONE kernel with device-side grid barriers
-// between stages, instead of ~60 dependent launches at the ~4 us
-// dispatch-latency floor. Valid when every stage fits one resident
-// grid (blocks <= 256 on 256 CUs => all workgroups co-resident, so
-// the barrier cannot deadlock) and the dense preconditioner is in
-// use. Reduction tails reuse the CF fan-in machinery; stage
-// ordering/visibility comes from a generation-counter barrier with
-// agent-scope fences. The control block is written to mapped pinned
-// host memory by the last stage, so the host-side acceptance /
-// shrink logic (solve_postsync) proceeds after one stream sync.
-// ---------------------------------------------------------------------
-__device__ __forceinline__ void grid_barrier(unsigned int* cnt,
-                                             unsigned int* gen,
-                                             unsigned int nb) {
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  if (threadIdx.x == 0) {
-    const unsigned int g =
-        __hip_atomic_load(gen, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned int old = __hip_atomic_fetch_add(
-        cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (old == nb - 1) {
-      __hip_atomic_store(cnt, 0u, __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_fetch_add(gen, 1u, __ATOMIC_RELEASE,
-                             __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-      long spins = 0;
-      while (__hip_atomic_load(gen, __ATOMIC_ACQUIRE,
-                               __HIP_MEMORY_SCOPE_AGENT) == g) {
-        __builtin_amdgcn_s_sleep(8);
-        if (++spins > 400000000L) __builtin_trap();  // lost-block guard
-      }
-    }
-  }
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-// k_ctrl_candidate's body as a device function (single thread).
-__device__ void ctrl_candidate_logic(double* ctrl) {
-  if (ctrl[C_STATUS] != (double)ST_TCG_STOP) return;
-  const double radius = ctrl[C_RADIUS];
-  const int hlen = (int)ctrl[C_HLEN];
-  double dm = 0.0;
-  int jstar = -1;
-  double taustar = 0.0;
-  for (int j = 0; j < hlen && j < MAX_TCG; ++j) {
-    const double z_r = ctrl[H_ZR(j)];
-    const double d_Hd = ctrl[H_DHD(j)];
-    const double e_Pe = ctrl[H_EPE(j)];
-    const double e_Pd = ctrl[H_EPD(j)];
-    const double d_Pd = ctrl[H_DPD(j)];
-    const double alpha = z_r / d_Hd;
-    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
-    if (d_Hd <= 0.0 || e_Pe_new >= radius * radius) {
-      const double disc = e_Pd * e_Pd + d_Pd * (radius * radius - e_Pe);
-      const double tau = (d_Pd > 0.0)
-          ? (-e_Pd + sqrt(fmax(disc, 0.0))) / d_Pd : 0.0;
-      dm += tau * z_r - 0.5 * tau * tau * d_Hd;
-      jstar = j;
-      taustar = tau;
-      break;
-    }
-    dm += 0.5 * alpha * z_r;
-  }
-  if (jstar < 0) {
-    ctrl[C_USE_CURRENT] = 1.0;
-  } else {
-    ctrl[C_USE_CURRENT] = 0.0;
-    ctrl[C_JSTAR] = (double)jstar;
-    ctrl[C_TAUSTAR] = taustar;
-  }
-  ctrl[C_DM] = dm;
-  ctrl[C_DOT0] = 0.0;
-  ctrl[C_DOT2] = 0.0;
-}
-
-template <int D, int R>
-__global__ void k_solve_persist(
-    const int* __restrict__ q_rp, const int* __restrict__ q_ci,
-    const double* __restrict__ q_vals, const double* __restrict__ X,
-    const double* __restrict__ G,   // linear term (read; may be null)
-    double* __restrict__ Gw,        // == G when assembling here, else null
-    const double* __restrict__ gE0, const long* __restrict__ g_local_pose,
-    const long* __restrict__ g_nbr_slot, const double* __restrict__ nbr,
-    const double* __restrict__ g_w, int g_ne,
-    const float* __restrict__ Minv, double* __restrict__ eta,
-    double* __restrict__ rvec, double* __restrict__ delta,
-    double* __restrict__ z, double* __restrict__ Hd,
-    double* __restrict__ eta_snap, double* __restrict__ delta_snap,
-    double* __restrict__ step, double* __restrict__ Xprop,
-    double* __restrict__ ctrl, double* __restrict__ ctrl_host,
-    unsigned int* __restrict__ gbar, int n, int N, long total,
-    int max_inner, double tol, double Delta0, double theta, double kappa,
-    double accept_rho, int jmul, int full) {
-  constexpr int dh = D + 1;
-  const int tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const long stride = (long)gridDim.x * blockDim.x;
-  const unsigned int nb = gridDim.x;
-  unsigned int* cnt = gbar;
-  unsigned int* gen = gbar + 1;
-#define PSTAMP(i) \
-  if (blockIdx.x == 0 && threadIdx.x == 0) \
-    ctrl_host[CTRL_SIZE + (i)] = (double)wall_clock64();
-  PSTAMP(0)
-
-  if (full) {
-  // --- S0: zero ctrl (+ G when assembling) --------------------------
-  for (long t = tid; t < CTRL_SIZE; t += stride) ctrl[t] = 0.0;
-  if (Gw) {
-    for (long t = tid; t < total; t += stride) Gw[t] = 0.0;
-    grid_barrier(cnt, gen, nb);
-    // --- S0b: G assembly (edge-element stride loop, scatter-add) ----
-    const long ge = (long)g_ne * dh * R;
-    for (long i = tid; i < ge; i += stride) {
-      const int e = (int)(i / (dh * R));
-      const int t = (int)(i % (dh * R));
-      const int c = t / R, k = t % R;
-      const double* Ee = gE0 + (size_t)e * dh * dh;
-      const double* Xn = nbr + (size_t)g_nbr_slot[e] * dh * R;
-      double acc = 0.0;
-      #pragma unroll
-      for (int b = 0; b < dh; ++b)
-        acc = fma(Ee[c * dh + b], Xn[b * R + k], acc);
-      atomicAdd(&Gw[((size_t)g_local_pose[e] * dh + c) * R + k],
-                -g_w[e] * acc);
-    }
-  }
-  grid_barrier(cnt, gen, nb);
-  PSTAMP(1)
-
-  // --- S1: gradient phase (pose threads) + init tail ----------------
-  {
-    double d_fx = 0.0, d_gn = 0.0, d_gx = 0.0;
-    if (tid < n) {
-      double acc[dh][R];
-      #pragma unroll
-      for (int c = 0; c < dh; ++c)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) acc[c][k] = 0.0;
-      const int s0 = q_rp[tid], e0 = q_rp[tid + 1];
-      for (int p = s0; p < e0; ++p) {
-        const double* B = q_vals + (size_t)p * dh * dh;
-        const double* Vj = X + (size_t)q_ci[p] * dh * R;
-        #pragma unroll
-        for (int c = 0; c < dh; ++c)
-          #pragma unroll
-          for (int cc = 0; cc < dh; ++cc) {
-            const double b = B[c * dh + cc];
-            #pragma unroll
-            for (int k = 0; k < R; ++k)
-              acc[c][k] = fma(b, Vj[cc * R + k], acc[c][k]);
-          }
-      }
-      const double* Xi = X + (size_t)tid * dh * R;
-      const double* Gi = G ? G + (size_t)tid * dh * R : nullptr;
-      #pragma unroll
-      for (int c = 0; c < dh; ++c)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) {
-          double g = Gi ? Gi[c * R + k] : 0.0;
-          double v = acc[c][k] + g;
-          acc[c][k] = v;
-          d_fx = fma(v, Xi[c * R + k], d_fx);
-          d_gx = fma(g, Xi[c * R + k], d_gx);
-        }
-      // tangent projection at X
-      double S[D][D];
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int b = 0; b < D; ++b) {
-          double sv = 0.0;
-          #pragma unroll
-          for (int k = 0; k < R; ++k)
-            sv = fma(Xi[a * R + k], acc[b][k], sv);
-          S[a][b] = sv;
-        }
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int b = a; b < D; ++b) {
-          const double sv = 0.5 * (S[a][b] + S[b][a]);
-          S[a][b] = sv;
-          S[b][a] = sv;
-        }
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) {
-          double v = acc[a][k];
-          #pragma unroll
-          for (int b = 0; b < D; ++b)
-            v = fma(-S[a][b], Xi[b * R + k], v);
-          acc[a][k] = v;
-        }
-      double* Ri = rvec + (size_t)tid * dh * R;
-      #pragma unroll
-      for (int c = 0; c < dh; ++c)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) {
-          Ri[c * R + k] = acc[c][k];
-          d_gn = fma(acc[c][k], acc[c][k], d_gn);
-        }
-    }
-    if (tid < total) z[tid] = 0.0;  // j-split precond accumulates
-    block_reduce_atomic(d_fx, ctrl + C_DOT0);
-    block_reduce_atomic(d_gn, ctrl + C_DOT1);
-    block_reduce_atomic(d_gx, ctrl + C_DOT2);
-    if (fanin_last_block(ctrl) && threadIdx.x == 0) {
-      // k_ctrl_init body
-      const double fX = 0.5 * (ctrl_load(ctrl + C_DOT0)
-                               + ctrl_load(ctrl + C_DOT2));
-      const double gn0sq = ctrl_load(ctrl + C_DOT1);
-      ctrl_store(ctrl + C_FX, fX);
-      ctrl_store(ctrl + C_GN0SQ, gn0sq);
-      ctrl_store(ctrl + C_RR, gn0sq);
-      const double norm_r0 = sqrt(gn0sq);
-      ctrl_store(ctrl + C_BOUND, norm_r0 * fmin(pow(norm_r0, theta), kappa));
-      ctrl_store(ctrl + C_RADIUS, Delta0);
-      ctrl_store(ctrl + C_EPE, 0.0);
-      ctrl_store(ctrl + C_EPD, 0.0);
-      ctrl_store(ctrl + C_ITER, 0.0);
-      ctrl_store(ctrl + C_J, 0.0);
-      ctrl_store(ctrl + C_USE_CURRENT, 0.0);
-      ctrl_store(ctrl + C_STOP_PENDING, 0.0);
-      ctrl_store(ctrl + C_BETA, 0.0);
-      ctrl_store(ctrl + C_STATUS, (norm_r0 < tol) ? (double)ST_NO_UPDATE
-                                                  : (double)ST_RUN);
-      ctrl_store(ctrl + C_DOT0, 0.0);
-      ctrl_store(ctrl + C_DOT1, 0.0);
-      ctrl_store(ctrl + C_DOT2, 0.0);
-      ctrl_store(ctrl + C_DOT3, 0.0);
-    }
-  }
-  grid_barrier(cnt, gen, nb);
-  }  // full: assembly + gradient phase
-  PSTAMP(2)
-
-  if (full && ctrl[C_STATUS] == (double)ST_RUN) {
-    // --- S2: z0 = P_X(Minv r0), <z0,r0> -> tail_z0; delta0 = -z0 ----
-    // j-split dense apply: the extra (jmul-1)*total threads of the
-    // widened grid each take a chunk of the j-range (the apply is
-    // latency-bound on the L2-cold pass over Minv, so memory-level
-    // parallelism is the lever); 4 accumulator chains per thread.
-    if (tid < (long)total * jmul) {
-      const long e = tid % total;
-      const int q = (int)(tid / total);
-      const int i = (int)(e / R), k = (int)(e % R);
-      const int jchunk = (N + jmul - 1) / jmul;
-      const int jlo = q * jchunk, jhi = min(N, jlo + jchunk);
-      double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-      int jj = jlo;
-      for (; jj + 4 <= jhi; jj += 4) {
-        a0 = fma((double)Minv[(size_t)(jj + 0) * N + i],
-                 rvec[(size_t)(jj + 0) * R + k], a0);
-        a1 = fma((double)Minv[(size_t)(jj + 1) * N + i],
-                 rvec[(size_t)(jj + 1) * R + k], a1);
-        a2 = fma((double)Minv[(size_t)(jj + 2) * N + i],
-                 rvec[(size_t)(jj + 2) * R + k], a2);
-        a3 = fma((double)Minv[(size_t)(jj + 3) * N + i],
-                 rvec[(size_t)(jj + 3) * R + k], a3);
-      }
-      for (; jj < jhi; ++jj)
-        a0 = fma((double)Minv[(size_t)jj * N + i],
-                 rvec[(size_t)jj * R + k], a0);
-      const double part = (a0 + a1) + (a2 + a3);
-      if (jmul == 1) z[e] = part;
-      else atomicAdd(&z[e], part);
-    }
-    grid_barrier(cnt, gen, nb);
-    {
-      double d0 = 0.0;
-      if (tid < n) {
-        const double* Xi = X + (size_t)tid * dh * R;
-        double* Zi = z + (size_t)tid * dh * R;
-        const double* Ri = rvec + (size_t)tid * dh * R;
-        double Vt[dh][R];
-        #pragma unroll
-        for (int c = 0; c < dh; ++c)
-          #pragma unroll
-          for (int k = 0; k < R; ++k) Vt[c][k] = Zi[c * R + k];
-        double S[D][D];
-        #pragma unroll
-        for (int a = 0; a < D; ++a)
-          #pragma unroll
-          for (int b = 0; b < D; ++b) {
-            double sv = 0.0;
-            #pragma unroll
-            for (int k = 0; k < R; ++k) sv = fma(Xi[a * R + k], Vt[b][k], sv);
-            S[a][b] = sv;
-          }
-        #pragma unroll
-        for (int a = 0; a < D; ++a)
-          #pragma unroll
-          for (int b = a; b < D; ++b) {
-            const double sv = 0.5 * (S[a][b] + S[b][a]);
-            S[a][b] = sv;
-            S[b][a] = sv;
-          }
-        #pragma unroll
-        for (int a = 0; a < D; ++a)
-          #pragma unroll
-          for (int k = 0; k < R; ++k) {
-            double v = Vt[a][k];
-            #pragma unroll
-            for (int b = 0; b < D; ++b)
-              v = fma(-S[a][b], Xi[b * R + k], v);
-            Vt[a][k] = v;
-          }
-        #pragma unroll
-        for (int c = 0; c < dh; ++c)
-          #pragma unroll
-          for (int k = 0; k < R; ++k) {
-            Zi[c * R + k] = Vt[c][k];
-            d0 = fma(Vt[c][k], Ri[c * R + k], d0);
-          }
-      }
-      block_reduce_atomic(d0, ctrl + C_DOT0);
-      if (fanin_last_block(ctrl) && threadIdx.x == 0)
-        ctrl_tail_z0(ctrl);
-    }
-    grid_barrier(cnt, gen, nb);
-    if (tid < total) delta[tid] = -z[tid];
-  }  // full: z0 phase
-  PSTAMP(3)
-
-  {
-    // --- S3: the tCG loop -------------------------------------------
-    for (int it = 0; it < max_inner; ++it) {
-      grid_barrier(cnt, gen, nb);  // prior delta writes visible
-      if (ctrl[C_STATUS] != (double)ST_RUN) break;
-
-      // H: Hd = P_X(Q delta), d_Qd -> C_DOT0, tail_alpha
-      {
-        double d0 = 0.0;
-        if (tid < n) {
-          double acc[dh][R];
-          #pragma unroll
-          for (int c = 0; c < dh; ++c)
-            #pragma unroll
-            for (int k = 0; k < R; ++k) acc[c][k] = 0.0;
-          const int s0 = q_rp[tid], e0 = q_rp[tid + 1];
-          for (int p = s0; p < e0; ++p) {
-            const double* B = q_vals + (size_t)p * dh * dh;
-            const double* Vj = delta + (size_t)q_ci[p] * dh * R;
-            #pragma unroll
-            for (int c = 0; c < dh; ++c)
-              #pragma unroll
-              for (int cc = 0; cc < dh; ++cc) {
-                const double b = B[c * dh + cc];
-                #pragma unroll
-                for (int k = 0; k < R; ++k)
-                  acc[c][k] = fma(b, Vj[cc * R + k], acc[c][k]);
-              }
-          }
-          const double* Xi = X + (size_t)tid * dh * R;
-          double S[D][D];
-          #pragma unroll
-          for (int a = 0; a < D; ++a)
-            #pragma unroll
-            for (int b = 0; b < D; ++b) {
-              double sv = 0.0;
-              #pragma unroll
-              for (int k = 0; k < R; ++k)
-                sv = fma(Xi[a * R + k], acc[b][k], sv);
-              S[a][b] = sv;
-            }
-          #pragma unroll
-          for (int a = 0; a < D; ++a)
-            #pragma unroll
-            for (int b = a; b < D; ++b) {
-              const double sv = 0.5 * (S[a][b] + S[b][a]);
-              S[a][b] = sv;
-              S[b][a] = sv;
-            }
-          #pragma unroll
-          for (int a = 0; a < D; ++a)
-            #pragma unroll
-            for (int k = 0; k < R; ++k) {
-              double v = acc[a][k];
-              #pragma unroll
-              for (int b = 0; b < D; ++b)
-                v = fma(-S[a][b], Xi[b * R + k], v);
-              acc[a][k] = v;
-            }
-          double* Oi = Hd + (size_t)tid * dh * R;
-          const double* Wi = delta + (size_t)tid * dh * R;
-          #pragma unroll
-          for (int c = 0; c < dh; ++c)
-            #pragma unroll
-            for (int k = 0; k < R; ++k) {
-              Oi[c * R + k] = acc[c][k];
-              d0 = fma(acc[c][k], Wi[c * R + k], d0);
-            }
-        }
-        block_reduce_atomic(d0, ctrl + C_DOT0);
-        if (fanin_last_block(ctrl) && threadIdx.x == 0)
-          ctrl_tail_alpha(ctrl);
-      }
-      grid_barrier(cnt, gen, nb);
-
-      // U: eta/r update + snapshots, rr -> C_DOT1, tail_rr
-      {
-        const double coef = ctrl[C_COEF];
-        const int stop_pending = (int)ctrl[C_STOP_PENDING];
-        const int j = (int)ctrl[C_ITER];
-        double rr = 0.0;
-        if (tid < total) z[tid] = 0.0;  // next j-split apply accumulates
-        if (tid < total) {
-          const double dl = delta[tid];
-          const double et = (j == 0) ? 0.0 : eta[tid];
-          __builtin_nontemporal_store(et,
-              &eta_snap[(size_t)j * total + tid]);
-          __builtin_nontemporal_store(dl,
-              &delta_snap[(size_t)j * total + tid]);
-          eta[tid] = fma(coef, dl, et);
-          if (!stop_pending) {
-            const double rn = fma(coef, Hd[tid], rvec[tid]);
-            rvec[tid] = rn;
-            rr = rn * rn;
-          }
-        }
-        if (!stop_pending) block_reduce_atomic(rr, ctrl + C_DOT1);
-        if (fanin_last_block(ctrl) && threadIdx.x == 0)
-          ctrl_tail_rr(ctrl);
-      }
-      grid_barrier(cnt, gen, nb);
-      if (ctrl[C_STATUS] != (double)ST_RUN) break;
-
-      // P: z = Minv r (j-split dense fp32 apply; see z0 stage)
-      if (tid < (long)total * jmul) {
-        const long e = tid % total;
-        const int q = (int)(tid / total);
-        const int i = (int)(e / R), k = (int)(e % R);
-        const int jchunk = (N + jmul - 1) / jmul;
-        const int jlo = q * jchunk, jhi = min(N, jlo + jchunk);
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-        int jj = jlo;
-        for (; jj + 4 <= jhi; jj += 4) {
-          a0 = fma((double)Minv[(size_t)(jj + 0) * N + i],
-                   rvec[(size_t)(jj + 0) * R + k], a0);
-          a1 = fma((double)Minv[(size_t)(jj + 1) * N + i],
-                   rvec[(size_t)(jj + 1) * R + k], a1);
-          a2 = fma((double)Minv[(size_t)(jj + 2) * N + i],
-                   rvec[(size_t)(jj + 2) * R + k], a2);
-          a3 = fma((double)Minv[(size_t)(jj + 3) * N + i],
-                   rvec[(size_t)(jj + 3) * R + k], a3);
-        }
-        for (; jj < jhi; ++jj)
-          a0 = fma((double)Minv[(size_t)jj * N + i],
-                   rvec[(size_t)jj * R + k], a0);
-        const double part = (a0 + a1) + (a2 + a3);
-        if (jmul == 1) z[e] = part;
-        else atomicAdd(&z[e], part);
-      }
-      grid_barrier(cnt, gen, nb);
-
-      // J: project z at X, <z, r> -> C_DOT0, tail_beta
-      {
-        double d0 = 0.0;
-        if (tid < n) {
-          const double* Xi = X + (size_t)tid * dh * R;
-          double* Zi = z + (size_t)tid * dh * R;
-          const double* Ri = rvec + (size_t)tid * dh * R;
-          double Vt[dh][R];
-          #pragma unroll
-          for (int c = 0; c < dh; ++c)
-            #pragma unroll
-            for (int k = 0; k < R; ++k) Vt[c][k] = Zi[c * R + k];
-          double S[D][D];
-          #pragma unroll
-          for (int a = 0; a < D; ++a)
-            #pragma unroll
-            for (int b = 0; b < D; ++b) {
-              double sv = 0.0;
-              #pragma unroll
-              for (int k = 0; k < R; ++k)
-                sv = fma(Xi[a * R + k], Vt[b][k], sv);
-              S[a][b] = sv;
-            }
-          #pragma unroll
-          for (int a = 0; a < D; ++a)
-            #pragma unroll
-            for (int b = a; b < D; ++b) {
-              const double sv = 0.5 * (S[a][b] + S[b][a]);
-              S[a][b] = sv;
-              S[b][a] = sv;
-            }
-          #pragma unroll
-          for (int a = 0; a < D; ++a)
-            #pragma unroll
-            for (int k = 0; k < R; ++k) {
-              double v = Vt[a][k];
-              #pragma unroll
-              for (int b = 0; b < D; ++b)
-                v = fma(-S[a][b], Xi[b * R + k], v);
-              Vt[a][k] = v;
-            }
-          #pragma unroll
-          for (int c = 0; c < dh; ++c)
-            #pragma unroll
-            for (int k = 0; k < R; ++k) {
-              Zi[c * R + k] = Vt[c][k];
-              d0 = fma(Vt[c][k], Ri[c * R + k], d0);
-            }
-        }
-        block_reduce_atomic(d0, ctrl + C_DOT0);
-        if (fanin_last_block(ctrl) && threadIdx.x == 0)
-          ctrl_tail_beta(ctrl);
-      }
-      grid_barrier(cnt, gen, nb);
-
-      // D: delta = beta*delta - z
-      if (tid < total)
-        delta[tid] = fma(ctrl[C_BETA], delta[tid], -z[tid]);
-    }
-    grid_barrier(cnt, gen, nb);
-    PSTAMP(4)
-    if (full && blockIdx.x == 0 && threadIdx.x == 0) {
-      // k_ctrl_tcg_end body
-      if (ctrl[C_STATUS] == (double)ST_RUN) {
-        ctrl_store(ctrl + C_STATUS, (double)ST_TCG_STOP);
-        ctrl_store(ctrl + C_J, ctrl[C_ITER]);
-        ctrl_store(ctrl + C_HLEN, ctrl[C_ITER]);
-        ctrl_store(ctrl + C_USE_CURRENT, 1.0);
-      }
-      ctrl_candidate_logic(ctrl);
-    }
-    grid_barrier(cnt, gen, nb);
-  }
-
-  // --- S4: first candidate: form step, retract, evaluate, accept ----
-  PSTAMP(5)
-  if (full && ctrl[C_STATUS] == (double)ST_TCG_STOP) {
-    if (tid < total) {
-      if (ctrl[C_USE_CURRENT] != 0.0) {
-        step[tid] = eta[tid];
-      } else {
-        const int j = (int)ctrl[C_JSTAR];
-        const double tau = ctrl[C_TAUSTAR];
-        step[tid] = fma(tau, delta_snap[(size_t)j * total + tid],
-                        eta_snap[(size_t)j * total + tid]);
-      }
-    }
-    grid_barrier(cnt, gen, nb);
-    // polar retraction Xprop = polar(X + step)
-    if (tid < n) {
-      double Mt[dh][R];
-      const double* Ai = X + (size_t)tid * dh * R;
-      const double* Bi = step + (size_t)tid * dh * R;
-      #pragma unroll
-      for (int c = 0; c < dh; ++c)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) Mt[c][k] = Ai[c * R + k] + Bi[c * R + k];
-      double S[D][D];
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int b = 0; b < D; ++b) {
-          double s = 0.0;
-          #pragma unroll
-          for (int k = 0; k < R; ++k) s = fma(Mt[a][k], Mt[b][k], s);
-          S[a][b] = s;
-        }
-      double Gi2[D][D];
-      spd_inv_sqrt<D>(S, Gi2);
-      double* Oi = Xprop + (size_t)tid * dh * R;
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) {
-          double s = 0.0;
-          #pragma unroll
-          for (int b = 0; b < D; ++b) s = fma(Gi2[a][b], Mt[b][k], s);
-          Oi[a * R + k] = s;
-        }
-      #pragma unroll
-      for (int k = 0; k < R; ++k) Oi[D * R + k] = Mt[D][k];
-    }
-    grid_barrier(cnt, gen, nb);
-    // f(Xprop) dots: <Q Xprop, Xprop> -> C_DOT0, <G, Xprop> -> C_DOT2
-    {
-      double d0 = 0.0, d1 = 0.0;
-      if (tid < n) {
-        double acc[dh][R];
-        #pragma unroll
-        for (int c = 0; c < dh; ++c)
-          #pragma unroll
-          for (int k = 0; k < R; ++k) acc[c][k] = 0.0;
-        const int s0 = q_rp[tid], e0 = q_rp[tid + 1];
-        for (int p = s0; p < e0; ++p) {
-          const double* B = q_vals + (size_t)p * dh * dh;
-          const double* Vj = Xprop + (size_t)q_ci[p] * dh * R;
-          #pragma unroll
-          for (int c = 0; c < dh; ++c)
-            #pragma unroll
-            for (int cc = 0; cc < dh; ++cc) {
-              const double b = B[c * dh + cc];
-              #pragma unroll
-              for (int k = 0; k < R; ++k)
-                acc[c][k] = fma(b, Vj[cc * R + k], acc[c][k]);
-            }
-        }
-        const double* Vi = Xprop + (size_t)tid * dh * R;
-        const double* Gi = G ? G + (size_t)tid * dh * R : nullptr;
-        #pragma unroll
-        for (int c = 0; c < dh; ++c)
-          #pragma unroll
-          for (int k = 0; k < R; ++k) {
-            const double g = Gi ? Gi[c * R + k] : 0.0;
-            d0 = fma(acc[c][k], Vi[c * R + k], d0);
-            d1 = fma(g, Vi[c * R + k], d1);
-          }
-      }
-      block_reduce_atomic(d0, ctrl + C_DOT0);
-      block_reduce_atomic(d1, ctrl + C_DOT2);
-      if (fanin_last_block(ctrl) && threadIdx.x == 0) {
-        // k_ctrl_accept body
-        if (ctrl[C_STATUS] == (double)ST_TCG_STOP) {
-          const double fprop = 0.5 * ctrl_load(ctrl + C_DOT0)
-                               + ctrl_load(ctrl + C_DOT2);
-          ctrl_store(ctrl + C_DOT0, 0.0);
-          ctrl_store(ctrl + C_DOT2, 0.0);
-          ctrl_store(ctrl + C_FPROP, fprop);
-          const double fX = ctrl[C_FX];
-          const double dm = ctrl[C_DM];
-          const double rho = (fX - fprop) / fmax(dm, 1e-300);
-          ctrl_store(ctrl + C_RHO, rho);
-          if (rho > accept_rho && fprop <= fX)
-            ctrl_store(ctrl + C_STATUS, (double)ST_ACCEPTED);
-        }
-      }
-    }
-  }
-  grid_barrier(cnt, gen, nb);
-  PSTAMP(6)
-
-  // --- S5: publish the control block to the host --------------------
-  if (full && blockIdx.x == 0)
-    for (int t = threadIdx.x; t < CTRL_SIZE; t += blockDim.x)
-      ctrl_host[t] = ctrl_load(ctrl + t);
-  PSTAMP(7)
-#undef PSTAMP
-}
-
-// ---------------------------------------------------------------------
 // Single-wave tCG control kernels (device-side branch logic)
 // ---------------------------------------------------------------------
 __global__ void k_ctrl_init(double* ctrl, double tol, double Delta0,
@@ -1874,84 +1232,17 @@ __global__ void k_ctrl_init(double* ctrl, double tol, double Delta0,
   ctrl[C_DOT3] = 0.0;
 }
 
-// after z0 projection+dot (C_DOT0 = <z0, r0>)
-__global__ void k_ctrl_z0(double* ctrl) {
-  if (threadIdx.x != 0) return;
-  if (ctrl[C_STATUS] != (double)ST_RUN) return;
-  const double zr = ctrl[C_DOT0];
-  ctrl[C_ZR] = zr;
-  ctrl[C_DPD] = zr;
-  ctrl[C_DOT0] = 0.0;
+// Standalone launch of one control tail (ctrl_tail_z0/alpha/rr/beta):
+// what DPO_NO_CF=1 runs after the producing reduction kernel instead of
+// the tail fused into that kernel's last block.
+template <int CF>
+__global__ void k_ctrl_tail(double* ctrl) {
+  if (threadIdx.x == 0) run_ctrl_tail(CF, ctrl, nullptr);
 }
 
-// after Hd projection+dot (C_DOT0 = <delta, Hd>): alpha / boundary logic
-__global__ void k_ctrl_alpha(double* ctrl) {
-  if (threadIdx.x != 0) return;
-  if (ctrl[C_STATUS] != (double)ST_RUN) return;
-  const int j = (int)ctrl[C_ITER];
-  const double d_Hd = ctrl[C_DOT0];
-  ctrl[C_DOT0] = 0.0;
-  const double z_r = ctrl[C_ZR];
-  const double e_Pe = ctrl[C_EPE], e_Pd = ctrl[C_EPD], d_Pd = ctrl[C_DPD];
-  const double radius = ctrl[C_RADIUS];
-  // scalar history for radius-replay (shrink loop reuses the Krylov path)
-  ctrl[H_ZR(j)] = z_r;
-  ctrl[H_DHD(j)] = d_Hd;
-  ctrl[H_EPE(j)] = e_Pe;
-  ctrl[H_EPD(j)] = e_Pd;
-  ctrl[H_DPD(j)] = d_Pd;
-  const double alpha = z_r / d_Hd;
-  const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
-  if (d_Hd <= 0.0 || e_Pe_new >= radius * radius) {
-    const double disc = e_Pd * e_Pd + d_Pd * (radius * radius - e_Pe);
-    const double tau = (d_Pd > 0.0)
-        ? (-e_Pd + sqrt(fmax(disc, 0.0))) / d_Pd : 0.0;
-    ctrl[C_COEF] = tau;
-    ctrl[C_STOP_PENDING] = 1.0;
-  } else {
-    ctrl[C_COEF] = alpha;
-    ctrl[C_EPE] = e_Pe_new;
-    ctrl[C_STOP_PENDING] = 0.0;
-  }
-}
-
-// after k_tcg_update (C_DOT1 = ||r||^2 when continuing)
-__global__ void k_ctrl_rr(double* ctrl) {
-  if (threadIdx.x != 0) return;
-  if (ctrl[C_STATUS] != (double)ST_RUN) return;
-  const int j = (int)ctrl[C_ITER];
-  if (ctrl[C_STOP_PENDING] != 0.0) {
-    ctrl[C_STATUS] = (double)ST_TCG_STOP;
-    ctrl[C_J] = (double)j;         // truncated at snapshot j
-    ctrl[C_HLEN] = (double)(j + 1);
-    ctrl[C_USE_CURRENT] = 0.0;
-    return;
-  }
-  const double rr = ctrl[C_DOT1];
-  ctrl[C_DOT1] = 0.0;
-  ctrl[C_RR] = rr;
-  if (sqrt(rr) <= ctrl[C_BOUND]) {
-    ctrl[C_STATUS] = (double)ST_TCG_STOP;
-    ctrl[C_J] = (double)(j + 1);
-    ctrl[C_HLEN] = (double)(j + 1);
-    ctrl[C_USE_CURRENT] = 1.0;     // converged: step = current eta
-  }
-}
-
-// after z projection+dot (C_DOT0 = <z, r>): beta and delta scalars
-__global__ void k_ctrl_beta(double* ctrl) {
-  if (threadIdx.x != 0) return;
-  if (ctrl[C_STATUS] != (double)ST_RUN) return;
-  const double z_r_new = ctrl[C_DOT0];
-  ctrl[C_DOT0] = 0.0;
-  const double z_r = ctrl[C_ZR];
-  const double alpha = ctrl[C_COEF];
-  const double beta = z_r_new / z_r;
-  ctrl[C_BETA] = beta;
-  ctrl[C_EPD] = beta * (ctrl[C_EPD] + alpha * ctrl[C_DPD]);
-  ctrl[C_DPD] = z_r_new + beta * beta * ctrl[C_DPD];
-  ctrl[C_ZR] = z_r_new;
-  ctrl[C_ITER] += 1.0;
+template <int CF>
+static void launch_ctrl_tail(double* ctrl, hipStream_t s) {
+  hipLaunchKernelGGL((k_ctrl_tail<CF>), dim3(1), dim3(64), 0, s, ctrl);
 }
 
 // end of the unrolled loop: cap at max_inner
@@ -2424,20 +1715,16 @@ void dpo_ctrl_init(double* ctrl, double tol, double Delta0, double theta,
                      (hipStream_t)stream, ctrl, tol, Delta0, theta, kappa);
 }
 void dpo_ctrl_z0(double* ctrl, void* stream) {
-  hipLaunchKernelGGL(k_ctrl_z0, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                     ctrl);
+  launch_ctrl_tail<CF_Z0>(ctrl, (hipStream_t)stream);
 }
 void dpo_ctrl_alpha(double* ctrl, void* stream) {
-  hipLaunchKernelGGL(k_ctrl_alpha, dim3(1), dim3(64), 0,
-                     (hipStream_t)stream, ctrl);
+  launch_ctrl_tail<CF_ALPHA>(ctrl, (hipStream_t)stream);
 }
 void dpo_ctrl_rr(double* ctrl, void* stream) {
-  hipLaunchKernelGGL(k_ctrl_rr, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                     ctrl);
+  launch_ctrl_tail<CF_RR>(ctrl, (hipStream_t)stream);
 }
 void dpo_ctrl_beta(double* ctrl, void* stream) {
-  hipLaunchKernelGGL(k_ctrl_beta, dim3(1), dim3(64), 0, (hipStream_t)stream,
-                     ctrl);
+  launch_ctrl_tail<CF_BETA>(ctrl, (hipStream_t)stream);
 }
 void dpo_ctrl_tcg_end(double* ctrl, void* stream) {
   hipLaunchKernelGGL(k_ctrl_tcg_end, dim3(1), dim3(64), 0,
@@ -2530,6 +1817,74 @@ __global__ void k_eval_combine(double* __restrict__ ctrl,
   ctrl[C_DOT3] = 0.0;
 }
 
+// One cached hipGraph exec for a fixed-pointer enqueue sequence.
+struct GraphCache {
+  hipGraphExec_t exec = nullptr;
+  const void* key[4] = {};
+  int replays = 0;
+  // Periodic graph-exec refresh. The "degradation after a few hundred
+  // replays" this originally worked around is now attributed to the
+  // SDMA-node / launch-ordering bugs fixed by the fences and
+  // kernels-only bodies; the refresh is kept as cheap insurance
+  // (amortized ~1%) and is tunable via DPO_MAX_REPLAYS.
+  static int max_replays() {
+    static const int v = [] {
+      const char* e = getenv("DPO_MAX_REPLAYS");
+      return e ? atoi(e) : 128;
+    }();
+    return v;
+  }
+  void reset() {
+    if (exec) {
+      dpo_ignore(hipGraphExecDestroy(exec));
+      exec = nullptr;
+    }
+  }
+};
+
+// Replay the cached graph on stream s. On a key change (or past the
+// refresh limit) first re-record it: body(cap) enqueues the sequence on
+// the capture stream. Returns false — nothing enqueued on s — when
+// capture/instantiation is unavailable; the caller then runs eagerly.
+template <class Body>
+static bool graph_cache_launch(GraphCache& g, const void* const (&key)[4],
+                               hipStream_t cap, hipStream_t s, Body body) {
+  const bool match = g.exec && memcmp(key, g.key, sizeof(key)) == 0
+                     && g.replays < GraphCache::max_replays();
+  if (!match) {
+    g.reset();
+    g.replays = 0;
+    hipGraph_t graph = nullptr;
+    hipError_t rc = hipStreamBeginCapture(
+        cap, hipStreamCaptureModeThreadLocal);
+    if (rc == hipSuccess) {
+      body(cap);
+      rc = hipStreamEndCapture(cap, &graph);
+    }
+    // a failed capture can leave the stream capturing: close it out
+    hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
+    dpo_ignore(hipStreamIsCapturing(cap, &capst));
+    if (capst != hipStreamCaptureStatusNone) {
+      hipGraph_t dead = nullptr;
+      dpo_ignore(hipStreamEndCapture(cap, &dead));
+      if (dead) dpo_ignore(hipGraphDestroy(dead));
+    }
+    if (rc == hipSuccess && graph) {
+      rc = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+      dpo_ignore(hipGraphDestroy(graph));
+    }
+    dpo_ignore(hipGetLastError());  // clear sticky capture-related error state
+    if (rc != hipSuccess || !g.exec) {
+      g.exec = nullptr;
+      return false;
+    }
+    memcpy(g.key, key, sizeof(key));
+  }
+  g.replays++;
+  DPO_CHECK(hipGraphLaunch(g.exec, s));
+  return true;
+}
+
 struct DpoCtx {
   int n, d, r, dh, N, max_inner;
   long total;
@@ -2552,24 +1907,7 @@ struct DpoCtx {
   // hipGraph caches for the fixed-pointer round sequences. Keyed by the
   // operand pointers; invalidated whenever set_problem/set_gdata change
   // them (preconditioner refresh, Q rebuild keep the same buffers).
-  hipGraphExec_t solve_graph = nullptr;
-  const void* solve_key[4] = {};
-  int solve_replays = 0;
-  hipGraphExec_t eval_graph = nullptr;
-  const void* eval_key[4] = {};
-  int eval_replays = 0;
-  // Periodic graph-exec refresh. The "degradation after a few hundred
-  // replays" this originally worked around is now attributed to the
-  // SDMA-node / launch-ordering bugs fixed by the fences and
-  // kernels-only bodies above; the refresh is kept as cheap insurance
-  // (amortized ~1%) and is tunable via DPO_MAX_REPLAYS.
-  static int max_replays() {
-    static const int v = [] {
-      const char* e = getenv("DPO_MAX_REPLAYS");
-      return e ? atoi(e) : 128;
-    }();
-    return v;
-  }
+  GraphCache solve_graph, eval_graph;
   // private stream used only for RECORDING captures (the legacy default
   // stream cannot be captured); graphs replay on the caller's stream.
   hipStream_t cap_stream = nullptr;
@@ -2585,20 +1923,12 @@ struct DpoCtx {
   double* pend_X = nullptr;
   // data-flow fence slots (see k_fence_* above)
   unsigned int* fences = nullptr;
-  // grid-barrier state for the persistent tCG kernel: [count, generation]
-  unsigned int* gbar = nullptr;
   // fixed 3-double eval destination for the group fan-out path (a
   // stable pointer keeps the eval graph cache hot)
   double* eval3 = nullptr;
   void invalidate_graphs() {
-    if (solve_graph) {
-      dpo_ignore(hipGraphExecDestroy(solve_graph));
-      solve_graph = nullptr;
-    }
-    if (eval_graph) {
-      dpo_ignore(hipGraphExecDestroy(eval_graph));
-      eval_graph = nullptr;
-    }
+    solve_graph.reset();
+    eval_graph.reset();
   }
 };
 
@@ -2730,8 +2060,7 @@ void* dpo_ctx_create(int n, int d, int r, int max_inner) {
   // per-solve zeroing passes are dropped from the captured body
   DPO_CHECK(hipMemset(c->delta, 0, vb));
   DPO_CHECK(hipMemset(c->eta, 0, vb));
-  // +16 slots: persistent-kernel stage timestamps (DPO_DBG_PERSIST=1)
-  DPO_CHECK(hipHostMalloc(&c->ctrl_host, (CTRL_SIZE + 16) * sizeof(double)));
+  DPO_CHECK(hipHostMalloc(&c->ctrl_host, CTRL_SIZE * sizeof(double)));
   DPO_CHECK(hipHostGetDevicePointer((void**)&c->ctrl_host_dev,
                                     c->ctrl_host, 0));
   DPO_CHECK(hipStreamCreateWithFlags(&c->cap_stream,
@@ -2745,8 +2074,6 @@ void* dpo_ctx_create(int n, int d, int r, int max_inner) {
   DPO_CHECK(hipMalloc(&c->fences, F_NUM * sizeof(unsigned int)));
   DPO_CHECK(hipMemset(c->fences, 0, F_NUM * sizeof(unsigned int)));
   DPO_CHECK(hipMalloc(&c->eval3, 3 * sizeof(double)));
-  DPO_CHECK(hipMalloc(&c->gbar, 2 * sizeof(unsigned int)));
-  DPO_CHECK(hipMemset(c->gbar, 0, 2 * sizeof(unsigned int)));
   return c;
 }
 
@@ -2761,7 +2088,7 @@ void dpo_ctx_destroy(void* h) {
   if (c->start_event) dpo_ignore(hipEventDestroy(c->start_event));
   if (c->done_event) dpo_ignore(hipEventDestroy(c->done_event));
   dpo_ignore(hipFree(c->ctrl)); dpo_ignore(hipFree(c->G_buf)); dpo_ignore(hipHostFree(c->ctrl_host));
-  dpo_ignore(hipFree(c->fences)); dpo_ignore(hipFree(c->eval3)); dpo_ignore(hipFree(c->gbar));
+  dpo_ignore(hipFree(c->fences)); dpo_ignore(hipFree(c->eval3));
   delete c;
 }
 
@@ -2774,52 +2101,6 @@ void dpo_ctx_set_problem(void* h, const int* rp, const int* ci,
     c->invalidate_graphs();
   c->q_rp = rp; c->q_ci = ci; c->q_vals = vals;
   c->Gt = Gt; c->Minv = Minv; c->Ljac = Ljac;
-}
-
-static void launch_solve_persist(DpoCtx* c, const double* X,
-                                 const double* nbr, double tol,
-                                 double Delta0, double accept_rho,
-                                 hipStream_t s, int full) {
-  const int gvec = (int)((c->total + 255) / 256);
-  // replicate ctx_assemble_g's pointer logic (assembly itself runs
-  // inside the kernel); c->Gt must be correct for the host-driven
-  // shrink-loop replay in solve_postsync
-  const double* G;
-  double* Gw = nullptr;
-  if (nbr) {
-    if (c->g_ne) {
-      c->Gt = c->G_buf;
-      G = c->G_buf;
-      Gw = c->G_buf;
-    } else {
-      c->Gt = nullptr;
-      G = nullptr;
-    }
-  } else {
-    G = c->Gt;
-  }
-  // NOTE: widening the grid for j-split preconditioner stages was
-  // measured SLOWER under multi-agent concurrency (4 agents x 200
-  // workgroups oversubscribes the 256 CUs and the idle blocks' barrier
-  // spins starve real work) — keep the grid at one block per 256
-  // elements and rely on the 4-chain unroll for MLP.
-  const int jmul = 1;
-#define CASE_TP(D, R) \
-  if (c->d == D && c->r == R) { \
-    hipLaunchKernelGGL((k_solve_persist<D, R>), dim3(gvec * jmul), \
-                       dim3(256), 0, \
-                       s, c->q_rp, c->q_ci, c->q_vals, X, G, Gw, c->g_E0, \
-                       c->g_local_pose, c->g_nbr_slot, nbr, c->g_w, \
-                       c->g_ne, c->Minv, c->eta, c->rvec, c->delta, c->z, \
-                       c->Hd, c->eta_snap, c->delta_snap, c->step, \
-                       c->Xprop, c->ctrl, c->ctrl_host_dev, c->gbar, \
-                       c->n, c->N, c->total, c->max_inner, tol, Delta0, \
-                       1.0, 0.1, accept_rho, jmul, full); \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_TP)
-#undef CASE_TP
-  dpo_bad_shape(c->d, c->r);
 }
 
 // Enqueue the fixed pre-sync solve sequence (gradient, tCG, first
@@ -2839,39 +2120,9 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
   // lever. An earlier attempt at this fusion showed trajectory scatter
   // that was eventually root-caused to an LDS reuse race in
   // block_reduce_atomic plus the hipGraph ordering bugs (both fixed);
-  // DPO_NO_CF=1 restores the dedicated control kernels.
+  // DPO_NO_CF=1 runs each tail as a standalone k_ctrl_tail launch.
   static const bool no_cf = dpo_env_flag("DPO_NO_CF");
-  static const bool no_persist = dpo_env_flag("DPO_NO_PERSIST");
   fence_wait(c, F_SOLVE_IN, s);  // first node: block until inputs ready
-  // Persistent-kernel scope: by default the tCG LOOP runs as one
-  // kernel (k_solve_persist with full=0) between the grad/z0 and
-  // candidate launch sequences — measured fastest under multi-agent
-  // concurrency. DPO_PERSIST_FULL=1 fuses the ENTIRE pre-sync solve
-  // into the kernel (fewer launches but the in-kernel z0 dense-
-  // preconditioner apply is latency-bound on the L2-cold Minv pass,
-  // which the standalone j-split kernel hides better).
-  static const bool persist_full = dpo_env_flag("DPO_PERSIST_FULL");
-  // N cap: the in-kernel dense preconditioner apply (one element per
-  // thread, 4 load chains) only beats the standalone j-split kernel
-  // while Minv stays cache-resident; for larger problems the
-  // per-stage launch path's j-split apply sustains far higher
-  // bandwidth (measured: city10000/cubicle agents at N ~ 4600-6000
-  // were 4-8x slower under the persistent path).
-  // Round 2: the persistent kernel is now OPT-IN (DPO_PERSIST=1).
-  // After the gradient/eval fusion cut the staged path's launch count,
-  // A/B probes (gpurun_out/r2h_probe.log) measured the staged path at
-  // ~1.4 ms/round vs ~2.6 ms/round persistent on the 8-agent sphere2500
-  // bench: at 25-workgroup grids the in-kernel grid barriers cost
-  // 380-850 us per solve loop under multi-agent concurrency.
-  static const bool persist_opt_in = dpo_env_flag("DPO_PERSIST");
-  const bool persist_ok = persist_opt_in && !no_persist && !no_cf
-      && c->Minv != nullptr
-      && c->N <= 1500 && (total + 255) / 256 <= 256;
-  if (persist_ok && persist_full) {
-    launch_solve_persist(c, X, nbr, tol, Delta0, accept_rho, s, 1);
-    fence_signal(c, F_SOLVE_OUT, s);
-    return;
-  }
   if (nbr) ctx_assemble_g(c, nbr, s);
   dzero(c->ctrl, CTRL_SIZE, s);
 
@@ -2892,29 +2143,25 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
     ctx_precond(c, c->rvec, c->z, s);
     launch_proj_dots(X, c->z, nullptr, c->z, c->rvec, c->ctrl, n, d, r,
                      C_DOT0, -1, ST_RUN, s);
-    hipLaunchKernelGGL(k_ctrl_z0, dim3(1), dim3(64), 0, s, c->ctrl);
+    launch_ctrl_tail<CF_Z0>(c->ctrl, s);
   } else {
     ctx_precond_proj<CF_Z0>(c, X, s);
   }
   hipLaunchKernelGGL(k_tcg_delta, dim3(gvec), dim3(256), 0, s,
                      c->delta, c->z, c->ctrl, total);
 
-  if (persist_ok) {
-    // the whole tCG loop as one kernel (grid barriers between stages)
-    launch_solve_persist(c, X, nbr, tol, Delta0, accept_rho, s, 0);
-  } else
   for (int j = 0; j < c->max_inner; ++j) {
     if (no_cf) {
       launch_hess_fused<0>(c->q_rp, c->q_ci, c->q_vals, c->delta, X,
                            nullptr, c->Hd, c->delta, c->ctrl, n, d, r,
                            C_DOT0, -1, ST_RUN, s);
-      hipLaunchKernelGGL(k_ctrl_alpha, dim3(1), dim3(64), 0, s, c->ctrl);
+      launch_ctrl_tail<CF_ALPHA>(c->ctrl, s);
       hipLaunchKernelGGL((k_tcg_update<CF_NONE>),
                          dim3(blocks_for((total + 3) / 4, 256)),
                          dim3(256), 0, s, c->eta, c->rvec, c->delta,
                          c->Hd, c->eta_snap, c->delta_snap, c->ctrl,
                          total);
-      hipLaunchKernelGGL(k_ctrl_rr, dim3(1), dim3(64), 0, s, c->ctrl);
+      launch_ctrl_tail<CF_RR>(c->ctrl, s);
     } else {
       launch_hess_fused<0, CF_ALPHA>(
           c->q_rp, c->q_ci, c->q_vals, c->delta, X, nullptr, c->Hd,
@@ -2929,7 +2176,7 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
       ctx_precond(c, c->rvec, c->z, s);
       launch_proj_dots(X, c->z, nullptr, c->z, c->rvec, c->ctrl, n, d, r,
                        C_DOT0, -1, ST_RUN, s);
-      hipLaunchKernelGGL(k_ctrl_beta, dim3(1), dim3(64), 0, s, c->ctrl);
+      launch_ctrl_tail<CF_BETA>(c->ctrl, s);
     } else {
       ctx_precond_proj<CF_BETA>(c, X, s);
     }
@@ -2974,47 +2221,17 @@ static bool solve_presync(DpoCtx* c, double* X, const double* nbr,
   }
   const void* key[4] = {X, nbr, (const void*)(intptr_t)(tol * 1e9),
                         (const void*)(intptr_t)Delta0};
-  bool key_match = c->solve_graph && memcmp(key, c->solve_key,
-                                            sizeof(key)) == 0
-                   && c->solve_replays < DpoCtx::max_replays();
-  if (!key_match) {
-    if (c->solve_graph) {
-      dpo_ignore(hipGraphExecDestroy(c->solve_graph));
-      c->solve_graph = nullptr;
-    }
-    c->solve_replays = 0;
-    hipGraph_t graph = nullptr;
-    hipStream_t cs_ = c->cap_stream;
-    hipError_t rc = hipStreamBeginCapture(
-        cs_, hipStreamCaptureModeThreadLocal);
-    if (rc == hipSuccess) {
-      enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, cs_);
-      rc = hipStreamEndCapture(cs_, &graph);
-    }
-    hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
-    dpo_ignore(hipStreamIsCapturing(cs_, &capst));
-    if (capst != hipStreamCaptureStatusNone) {
-      hipGraph_t dead = nullptr;
-      dpo_ignore(hipStreamEndCapture(cs_, &dead));
-      if (dead) dpo_ignore(hipGraphDestroy(dead));
-    }
-    if (rc == hipSuccess && graph) {
-      rc = hipGraphInstantiate(&c->solve_graph, graph, nullptr, nullptr, 0);
-      dpo_ignore(hipGraphDestroy(graph));
-    }
-    dpo_ignore(hipGetLastError());  // clear sticky capture-related error state
-    if (rc != hipSuccess || !c->solve_graph) {
-      // capture unavailable: run eagerly on the caller's stream
-      c->solve_graph = nullptr;
-      enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, s);
-      fence_wait(c, F_SOLVE_OUT, s);
-      DPO_CHECK(hipStreamSynchronize(s));
-      return false;
-    }
-    memcpy(c->solve_key, key, sizeof(key));
+  const bool launched = graph_cache_launch(
+      c->solve_graph, key, c->cap_stream, s, [&](hipStream_t cs) {
+        enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, cs);
+      });
+  if (!launched) {
+    // capture unavailable: run eagerly on the caller's stream
+    enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, s);
+    fence_wait(c, F_SOLVE_OUT, s);
+    DPO_CHECK(hipStreamSynchronize(s));
+    return false;
   }
-  c->solve_replays++;
-  DPO_CHECK(hipGraphLaunch(c->solve_graph, s));
   // eager wait pins downstream stream work (and host syncs) to the
   // graph's actual completion even if the launch misordered
   fence_wait(c, F_SOLVE_OUT, s);
@@ -3143,15 +2360,6 @@ int dpo_round_solve_finish(void* h, int max_shrink, double* stats_out,
                            void* join_stream) {
   DpoCtx* c = (DpoCtx*)h;
   DPO_CHECK(hipStreamSynchronize(c->exec_stream));
-  static const bool dbg_persist = dpo_env_flag("DPO_DBG_PERSIST");
-  if (dbg_persist) {
-    const double* ts = c->ctrl_host + CTRL_SIZE;
-    fprintf(stderr, "[persist us] zeroG %.1f grad %.1f z0 %.1f loop %.1f"
-            " end %.1f cand %.1f pub %.1f\n",
-            (ts[1]-ts[0])/100.0, (ts[2]-ts[1])/100.0, (ts[3]-ts[2])/100.0,
-            (ts[4]-ts[3])/100.0, (ts[5]-ts[4])/100.0, (ts[6]-ts[5])/100.0,
-            (ts[7]-ts[6])/100.0);
-  }
   int st = solve_postsync(c, c->pend_X, c->pend_rho, max_shrink, 0,
                           stats_out, c->exec_stream);
   DPO_CHECK(hipEventRecord(c->done_event, c->exec_stream));
@@ -3181,10 +2389,6 @@ void dpo_eval_terms(void* h, const double* X, double* out_dev,
   DpoCtx* c = (DpoCtx*)h;
   hipStream_t s = (hipStream_t)stream;
   const int n = c->n, d = c->d, r = c->r;
-  const long total = c->total;
-  const int gvec = (int)((total + 255) / 256);
-  static const bool no_cf = dpo_env_flag("DPO_NO_CF");
-  (void)gvec; (void)total; (void)no_cf;
   // dot slots are pre-zeroed (zero-init at allocation; k_eval_combine
   // self-cleans after each eval; solves wipe the whole control block)
   // ONE fused kernel: Q@X + G, projection at X, and all three scalars
@@ -3251,44 +2455,12 @@ static void round_eval_impl(DpoCtx* c, const double* X, const double* nbr,
     return;
   }
   const void* key[4] = {X, nbr, out_dev, nullptr};
-  bool match = c->eval_graph && memcmp(key, c->eval_key, sizeof(key)) == 0
-               && c->eval_replays < DpoCtx::max_replays();
-  if (!match) {
-    if (c->eval_graph) {
-      dpo_ignore(hipGraphExecDestroy(c->eval_graph));
-      c->eval_graph = nullptr;
-    }
-    c->eval_replays = 0;
-    hipGraph_t graph = nullptr;
-    hipStream_t cs_ = c->cap_stream;
-    hipError_t rc = hipStreamBeginCapture(
-        cs_, hipStreamCaptureModeThreadLocal);
-    if (rc == hipSuccess) {
-      enqueue_eval_body(c, X, nbr, out_dev, cs_);
-      rc = hipStreamEndCapture(cs_, &graph);
-    }
-    hipStreamCaptureStatus capst = hipStreamCaptureStatusNone;
-    dpo_ignore(hipStreamIsCapturing(cs_, &capst));
-    if (capst != hipStreamCaptureStatusNone) {
-      hipGraph_t dead = nullptr;
-      dpo_ignore(hipStreamEndCapture(cs_, &dead));
-      if (dead) dpo_ignore(hipGraphDestroy(dead));
-    }
-    if (rc == hipSuccess && graph) {
-      rc = hipGraphInstantiate(&c->eval_graph, graph, nullptr, nullptr, 0);
-      dpo_ignore(hipGraphDestroy(graph));
-    }
-    dpo_ignore(hipGetLastError());  // clear sticky capture-related error state
-    if (rc != hipSuccess || !c->eval_graph) {
-      c->eval_graph = nullptr;
-      enqueue_eval_body(c, X, nbr, out_dev, s);
-      if (wait_out) fence_wait(c, F_EVAL_OUT, s);
-      return;
-    }
-    memcpy(c->eval_key, key, sizeof(key));
-  }
-  c->eval_replays++;
-  DPO_CHECK(hipGraphLaunch(c->eval_graph, s));
+  const bool launched = graph_cache_launch(
+      c->eval_graph, key, c->cap_stream, s, [&](hipStream_t cs) {
+        enqueue_eval_body(c, X, nbr, out_dev, cs);
+      });
+  // capture unavailable: run eagerly on the caller's stream
+  if (!launched) enqueue_eval_body(c, X, nbr, out_dev, s);
   if (wait_out) fence_wait(c, F_EVAL_OUT, s);
 }
 

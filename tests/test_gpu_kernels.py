@@ -489,6 +489,126 @@ def test_hess_wide_matches_narrow():
     assert abs(a["gn"] - b["gn"]) < 1e-5 * max(1.0, abs(a["gn"]))
 
 
+# Child program of test_no_cf_matches_fused_tails: a 2-agent driver run
+# plus single DeviceSolver solves of the grid_fixture problem (rebuilt
+# here, same seeds) at the radii given on the command line.
+_NO_CF_CHILD = """
+import json, sys
+import torch
+from dpo_amd.comm import Comm
+from dpo_amd.dist_driver import DistributedRBCDDriver
+from dpo_amd.manifold import LiftedSEManifold
+from dpo_amd.ops.hip_backend import DeviceSolver
+from dpo_amd.quadratic import QuadraticProblem, assemble_connection_laplacian
+from dpo_amd.synthetic import grid3d
+out = {}
+meas, n = grid3d(side=6, seed=3)
+drv = DistributedRBCDDriver(meas, n, 2, Comm(), r=5,
+    partition='contiguous', selection='colored', device='cuda:0')
+res = drv.run(max_iters=40, gradnorm_tol=0.0)
+out['driver'] = {'cost': res.final_cost, 'gn': res.final_gradnorm,
+                 't0': res.trace[0], 'iters': res.iterations}
+meas, n = grid3d(side=4, seed=0)
+d, r = 3, 5
+Q = assemble_connection_laplacian(meas, n, d)
+g = torch.Generator().manual_seed(0)
+X = torch.randn((d + 1) * n, r, dtype=torch.float64, generator=g)
+X = LiftedSEManifold(r, d, n).project(X)
+pd = QuadraticProblem(n, d, r, precond='jacobi')
+pd.set_q(Q.to('cuda:0'))
+pd._Lpre = pd._Lpre.contiguous()
+out['solves'] = []
+for Delta0 in map(float, sys.argv[1:]):
+    ds = DeviceSolver(n, d, r, 'cuda:0', max_inner=10)
+    Xd = X.clone().to('cuda:0')
+    st = ds.solve(pd, Xd, tol=1e-2, Delta0=Delta0)
+    out['solves'].append({'status': st['status'], 'f_opt': st['f_opt'],
+                          'shrinks': st['shrinks'],
+                          'hlen': int(ds._stats[7]),
+                          'X': Xd.cpu().flatten().tolist()})
+print(json.dumps(out))
+"""
+
+
+def test_no_cf_matches_fused_tails(grid_fixture):
+    """DPO_NO_CF=1 (each tCG control step as a standalone k_ctrl_tail
+    launch) must give the same solves as the default, where the same
+    ctrl_tail_* functions run fused into the last block of the producing
+    reduction kernel. Subprocesses: the knob is read once per process.
+
+    Solve radii on the grid_fixture problem, each first classified on
+    the CPU by the host optimizer:
+      100.0  the radius the other solver tests use. On this iterate
+             (f ~ 5.2e5) it is already smaller than the first full CG
+             step, so it truncates in iteration 0 like the next one.
+      1.0    boundary: STOP_PENDING branch of ctrl_tail_alpha/rr,
+             history length exactly 1.
+      1e4    interior: tCG converges (third iteration on the host),
+             the residual-bound branch of ctrl_tail_rr plus ctrl_tail_beta.
+    """
+    import json
+    import os
+    import subprocess
+    import sys
+    from dpo_amd.quadratic import QuadraticProblem
+    from dpo_amd.solver import QuadraticOptimizer, TRParams
+    from dpo_amd.types import OptAlgorithm
+    meas, n, d, r, Q, X, V = grid_fixture
+
+    def host_status(Delta0, max_inner):
+        ph = QuadraticProblem(n, d, r, precond="jacobi")
+        ph.set_q(Q)
+        tr = TRParams(tolerance=1e-2, initial_radius=Delta0,
+                      max_iterations=1, max_inner_iterations=max_inner)
+        opt = QuadraticOptimizer(ph, OptAlgorithm.RTR, tr)
+        opt.optimize(X.clone())
+        return opt.result.tcg_status
+
+    radii = [100.0, 1.0, 1e4]
+    # boundary radius: the host truncates at the boundary, and still does
+    # when allowed a single inner iteration, i.e. it is the first one
+    assert host_status(1.0, 10) == "exceeded_tr"
+    assert host_status(1.0, 1) == "exceeded_tr"
+    assert host_status(1e4, 10) == "converged"
+
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = {}
+    for no_cf in ("", "1"):
+        env = dict(os.environ)
+        env.pop("DPO_NO_CF", None)
+        if no_cf:
+            env["DPO_NO_CF"] = no_cf
+        p = subprocess.run([sys.executable, "-c", _NO_CF_CHILD]
+                           + [repr(x) for x in radii],
+                           capture_output=True, text=True, env=env,
+                           cwd=here, timeout=300)
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs[no_cf] = json.loads(p.stdout.strip().splitlines()[-1])
+
+    a, b = outs[""]["driver"], outs["1"]["driver"]
+    print("driver fused", a, "no_cf", b)
+    assert a["iters"] == b["iters"]
+    assert abs(a["t0"][0] - b["t0"][0]) < 1e-9 * max(1, abs(a["t0"][0]))
+    assert abs(a["cost"] - b["cost"]) < 1e-8 * max(1, abs(a["cost"]))
+    assert abs(a["gn"] - b["gn"]) < 1e-5 * max(1.0, abs(a["gn"]))
+
+    for Delta0, sa, sb in zip(radii, outs[""]["solves"], outs["1"]["solves"]):
+        Xa = torch.tensor(sa.pop("X"), dtype=torch.float64)
+        Xb = torch.tensor(sb.pop("X"), dtype=torch.float64)
+        print("Delta0", Delta0, "fused", sa, "no_cf", sb,
+              "max|dX|", float((Xa - Xb).abs().max()))
+        assert sa["status"] == sb["status"] == 2  # ST_ACCEPTED
+        assert sa["hlen"] == sb["hlen"]
+        assert sa["shrinks"] == sb["shrinks"]
+        assert abs(sa["f_opt"] - sb["f_opt"]) < 1e-5 * max(
+            1, abs(sa["f_opt"]))
+        assert torch.allclose(Xa, Xb, atol=1e-6)
+        if Delta0 == 1.0:
+            assert sa["hlen"] == 1
+        if Delta0 == 1e4:
+            assert sa["hlen"] > 1
+
+
 def test_chordal_soa_gpu_matches_cpu():
     """GPU chordal init (BSR-kernel PCG) matches the CPU run of the
     same algorithm and the direct reference-style solve."""
