@@ -590,7 +590,11 @@ __global__ void k_proj_wide(const double* __restrict__ X,
 // MODE 1 (no projection, no store): dots <QV, V> and <G, V> (the
 // trust-region candidate's f evaluation).
 // ---------------------------------------------------------------------
-template <int D, int R, int MODE, int CF = CF_NONE>
+// AUX = 1 (MODE 0 only) adds two optional side effects for the solve's
+// gradient launch: a second copy of the result in out2, and zero_out's
+// rows of this pose cleared. A template parameter, so that the tCG-loop
+// instantiations keep their register budget.
+template <int D, int R, int MODE, int CF = CF_NONE, int AUX = 0>
 __global__ void k_hess_fused(const int* __restrict__ row_ptr,
                              const int* __restrict__ col_idx,
                              const double* __restrict__ vals,
@@ -601,7 +605,9 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
                              const double* __restrict__ dotW,
                              double* __restrict__ ctrl,
                              int n, int dot_slot, int dot_slot2,
-                             int dot_slot3, int guard) {
+                             int dot_slot3, int guard,
+                             double* __restrict__ out2,
+                             double* __restrict__ zero_out) {
   if (guarded_off(ctrl, guard)) return;
   constexpr int dh = D + 1;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -690,17 +696,25 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
           acc[a][k] = v;
         }
       double* Oi = out + (size_t)i * dh * R;
+      double* O2 = (AUX && out2) ? out2 + (size_t)i * dh * R : nullptr;
       const double* Wi = dotW ? dotW + (size_t)i * dh * R : nullptr;
       #pragma unroll
       for (int c = 0; c < dh; ++c)
         #pragma unroll
         for (int k = 0; k < R; ++k) {
           Oi[c * R + k] = acc[c][k];
+          if (AUX && O2) O2[c * R + k] = acc[c][k];
           if (dot_slot >= 0) {
             const double w = Wi ? Wi[c * R + k] : acc[c][k];
             d0 = fma(acc[c][k], w, d0);
           }
         }
+      // the next j-split dense apply accumulates into this buffer
+      if (AUX && zero_out) {
+        double* Zi = zero_out + (size_t)i * dh * R;
+        #pragma unroll
+        for (int e = 0; e < dh * R; ++e) Zi[e] = 0.0;
+      }
     }
   }
   if (dot_slot >= 0) block_reduce_atomic(d0, ctrl + dot_slot);
@@ -723,7 +737,7 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
 // the cross-element tangent projection stages the acc tile and X tile
 // through LDS. Same math and dot-product contract as k_hess_fused.
 // ---------------------------------------------------------------------
-template <int D, int R, int MODE, int CF = CF_NONE>
+template <int D, int R, int MODE, int CF = CF_NONE, int AUX = 0>
 __global__ void k_hess_wide(const int* __restrict__ row_ptr,
                             const int* __restrict__ col_idx,
                             const double* __restrict__ vals,
@@ -734,7 +748,9 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
                             const double* __restrict__ dotW,
                             double* __restrict__ ctrl,
                             int n, int dot_slot, int dot_slot2,
-                            int dot_slot3, int guard) {
+                            int dot_slot3, int guard,
+                            double* __restrict__ out2,
+                            double* __restrict__ zero_out) {
   if (guarded_off(ctrl, guard)) return;
   constexpr int dh = D + 1;
   constexpr int TILE = dh * R;
@@ -792,6 +808,8 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
     }
     if (live) {
       out[(size_t)i * TILE + e] = o;
+      if (AUX && out2) out2[(size_t)i * TILE + e] = o;
+      if (AUX && zero_out) zero_out[(size_t)i * TILE + e] = 0.0;
       if (dot_slot >= 0) {
         const double w = dotW ? dotW[(size_t)i * TILE + e] : o;
         d0 = o * w;
@@ -1090,6 +1108,7 @@ __global__ void k_precond_jacobi(const double* __restrict__ L,
 // Fused tCG vector updates (guarded; coefficients read from ctrl):
 //   snapshot: eta_snap[j] = eta, delta_snap[j] = delta  (pre-update)
 //   eta += coef * delta;  if (!stop_pending) { r += alpha*Hd; rr+=r^2 }
+//   zero_out (optional) = 0
 // ---------------------------------------------------------------------
 // Two elements per thread: the kernel is a pure fp64 stream (4 reads
 // + 4 writes per element) and was memory-latency-bound at 1M-pose
@@ -1102,7 +1121,8 @@ __global__ void k_tcg_update(double* __restrict__ eta,
                              double* __restrict__ eta_snap,
                              double* __restrict__ delta_snap,
                              double* __restrict__ ctrl,
-                             long total) {
+                             long total,
+                             double* __restrict__ zero_out) {
   if (guarded_off(ctrl, ST_RUN)) return;
   const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const double coef = ctrl[C_COEF];
@@ -1123,6 +1143,10 @@ __global__ void k_tcg_update(double* __restrict__ eta,
       __builtin_nontemporal_store(et, &eta_snap[(size_t)j * total + i]);
       __builtin_nontemporal_store(dl, &delta_snap[(size_t)j * total + i]);
       eta[i] = fma(coef, dl, et);
+      // z is dead until the next j-split dense apply accumulates into
+      // it: clear it here instead of in a launch of its own (nullptr
+      // on the Jacobi path, which overwrites z)
+      if (zero_out) zero_out[i] = 0.0;
       if (!stop_pending) {
         const double rn = fma(coef, Hd[i], rvec[i]);
         rvec[i] = rn;
@@ -1530,30 +1554,33 @@ static inline bool hess_use_wide(int n) {
   return false;
 }
 
-template <int MODE, int CF = CF_NONE>
+template <int MODE, int CF = CF_NONE, int AUX = 0>
 static void launch_hess_fused(const int* rp, const int* ci,
                               const double* vals, const double* V,
                               const double* X, const double* G,
                               double* out, const double* dotW,
                               double* ctrl, int n, int d, int r,
                               int dot_slot, int dot_slot2, int guard,
-                              hipStream_t s, int dot_slot3 = -1) {
+                              hipStream_t s, int dot_slot3 = -1,
+                              double* out2 = nullptr,
+                              double* zero_out = nullptr) {
   const int grid = blocks_for(n, 256);
   const bool wide = hess_use_wide(n);
 #define CASE_HF(D, R) \
   if (d == D && r == R) { \
     if (wide) { \
       constexpr int PB = 256 / ((D + 1) * R); \
-      hipLaunchKernelGGL((k_hess_wide<D, R, MODE, CF>), \
+      hipLaunchKernelGGL((k_hess_wide<D, R, MODE, CF, AUX>), \
                          dim3(blocks_for(n, PB)), dim3(256), 0, s, \
                          rp, ci, vals, V, X, G, out, dotW, \
                          ctrl, n, dot_slot, dot_slot2, dot_slot3, \
-                         guard); \
+                         guard, out2, zero_out); \
     } else { \
-      hipLaunchKernelGGL((k_hess_fused<D, R, MODE, CF>), dim3(grid), \
+      hipLaunchKernelGGL((k_hess_fused<D, R, MODE, CF, AUX>), \
+                         dim3(grid), \
                          dim3(256), 0, s, rp, ci, vals, V, X, G, out, \
                          dotW, ctrl, n, dot_slot, dot_slot2, dot_slot3, \
-                         guard); \
+                         guard, out2, zero_out); \
     } \
     return; \
   }
@@ -1577,15 +1604,24 @@ __global__ void k_ctrl_to_host(const double* __restrict__ src,
   if (i < n) dst[i] = src[i];
 }
 
+// j-split so small problems still produce >= ~512 workgroups
+static inline int precond_dense_jsplit(int N) {
+  const int gx = blocks_for(N, 256);
+  int jsplit = 1;
+  while (gx * jsplit < 512 && jsplit < 32) jsplit *= 2;
+  return jsplit;
+}
+
+// prezeroed: the caller guarantees Z is already all-zero wherever the
+// j-split partial sums accumulate (the solve body folds that zeroing
+// into the kernel that runs just before).
 static void launch_precond_dense(const float* Minv, const double* V,
                                  double* Z, int N, int r,
                                  const double* ctrl, int guard,
-                                 hipStream_t s) {
+                                 hipStream_t s, bool prezeroed = false) {
   const int gx = blocks_for(N, 256);
-  // j-split so small problems still produce >= ~512 workgroups
-  int jsplit = 1;
-  while (gx * jsplit < 512 && jsplit < 32) jsplit *= 2;
-  if (jsplit > 1) {
+  const int jsplit = precond_dense_jsplit(N);
+  if (jsplit > 1 && !prezeroed) {
     // kernel (not hipMemsetAsync): this runs inside captured graphs,
     // which must stay free of SDMA nodes (see fence comment)
     hipLaunchKernelGGL(k_dzero, dim3(blocks_for((long)N * r, 256)),
@@ -1675,7 +1711,7 @@ void dpo_tcg_update(double* eta, double* rvec, const double* delta,
   hipLaunchKernelGGL((k_tcg_update<CF_NONE>),
                      dim3(blocks_for((total + 3) / 4, 256)),
                      dim3(256), 0, s, eta, rvec, delta, Hd, eta_snap,
-                     delta_snap, ctrl, total);
+                     delta_snap, ctrl, total, (double*)nullptr);
 }
 
 void dpo_tcg_delta(double* delta, const double* z, double* ctrl, long total,
@@ -1908,6 +1944,13 @@ struct DpoCtx {
   // operand pointers; invalidated whenever set_problem/set_gdata change
   // them (preconditioner refresh, Q rebuild keep the same buffers).
   GraphCache solve_graph, eval_graph;
+  // second segment of a segmented solve (see solve_segment()): the tCG
+  // iterations past the primary graph's + the tail. Same key and
+  // refresh rule as solve_graph; captured on first need.
+  GraphCache cont_graph;
+  // host-side statistics, updated where ctrl_host is read anyway
+  long n_solves = 0, n_conts = 0;
+  long hlen_hist[MAX_TCG + 1] = {};
   // private stream used only for RECORDING captures (the legacy default
   // stream cannot be captured); graphs replay on the caller's stream.
   hipStream_t cap_stream = nullptr;
@@ -1921,6 +1964,7 @@ struct DpoCtx {
   // state of an in-flight async solve
   double pend_tol = 0, pend_Delta0 = 0, pend_rho = 0;
   double* pend_X = nullptr;
+  const double* pend_nbr = nullptr;
   // data-flow fence slots (see k_fence_* above)
   unsigned int* fences = nullptr;
   // fixed 3-double eval destination for the group fan-out path (a
@@ -1928,6 +1972,7 @@ struct DpoCtx {
   double* eval3 = nullptr;
   void invalidate_graphs() {
     solve_graph.reset();
+    cont_graph.reset();
     eval_graph.reset();
   }
 };
@@ -1995,10 +2040,21 @@ static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s) {
   c->Gt = c->G_buf;
 }
 
+// The buffer the solve body must have cleared before each dense apply:
+// z when the apply is j-split (its partial sums accumulate), nullptr on
+// the Jacobi path and for an unsplit apply, which overwrite z.
+static inline double* ctx_prezero_z(const DpoCtx* c) {
+  return (c->Minv && precond_dense_jsplit(c->N) > 1) ? c->z : nullptr;
+}
+
+// Solve-body preconditioner apply into c->z. The dense apply relies on
+// the kernel in front of it (gradient k_hess_fused for z0, k_tcg_update
+// in the loop) having cleared ctx_prezero_z(c).
 static void ctx_precond(DpoCtx* c, const double* V, double* Z,
                         hipStream_t s) {
   if (c->Minv)
-    launch_precond_dense(c->Minv, V, Z, c->N, c->r, c->ctrl, ST_RUN, s);
+    launch_precond_dense(c->Minv, V, Z, c->N, c->r, c->ctrl, ST_RUN, s,
+                         /*prezeroed=*/true);
   else
     launch_precond_jacobi(c->Ljac, V, Z, c->n, c->dh, c->r, c->ctrl,
                           ST_RUN, s);
@@ -2103,43 +2159,71 @@ void dpo_ctx_set_problem(void* h, const int* rp, const int* ci,
   c->Gt = Gt; c->Minv = Minv; c->Ljac = Ljac;
 }
 
-// Enqueue the fixed pre-sync solve sequence (gradient, tCG, first
-// candidate + acceptance test). Capturable as one hipGraph: every
-// operand pointer is stable across rounds by construction.
-static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
-                               double tol, double Delta0,
-                               double accept_rho, hipStream_t s) {
+// DPO_TCG_SEG=K: tCG iterations in the primary solve graph. The solve
+// graph is static, so every iteration it holds is launched whether or
+// not tCG has already stopped (a stopped iteration is 5-6 guarded no-op
+// launches at the dispatch floor each). With K < max_inner the primary
+// graph holds only K iterations; the rare solve still running after
+// them gets the rest from a second (continuation) graph, launched by
+// the host after the sync it performs anyway. 0 or >= max_inner: one
+// graph with every iteration. Unset: 3 with the dense preconditioner
+// (small, launch-bound agents: tCG stops after 2-4 iterations), one
+// graph with block-Jacobi (large agents: tCG usually runs to the cap,
+// so nearly every solve would continue). Both from the measured
+// iteration histograms, docs/DESIGN.md section 3.
+#define DPO_TCG_SEG_DENSE 3
+static int solve_segment(const DpoCtx* c) {
+  static const int env = [] {
+    const char* v = getenv("DPO_TCG_SEG");
+    return v ? atoi(v) : -1;
+  }();
+  const int seg = env >= 0 ? env : (c->Minv ? DPO_TCG_SEG_DENSE : 0);
+  return (seg <= 0 || seg >= c->max_inner) ? c->max_inner : seg;
+}
+
+// The solve sequence (gradient, tCG, first candidate + acceptance test)
+// in three pieces; every operand pointer is stable across rounds by
+// construction, so any concatenation of them is capturable as a
+// hipGraph.
+//
+// Fused control tails (CF_*): the tCG scalar decisions run in the
+// last-arriving block of the producing reduction kernel instead of a
+// dedicated single-wave kernel, removing 3 of 8 launches per tCG
+// iteration. The ~4 us/launch dispatch latency floor is what bounds
+// these small-agent solves (see profiles/), so launch count is the
+// lever. An earlier attempt at this fusion showed trajectory scatter
+// that was eventually root-caused to an LDS reuse race in
+// block_reduce_atomic plus the hipGraph ordering bugs (both fixed);
+// DPO_NO_CF=1 runs each tail as a standalone k_ctrl_tail launch.
+static bool solve_no_cf() {
+  static const bool no_cf = dpo_env_flag("DPO_NO_CF");
+  return no_cf;
+}
+
+// Head: G assembly, gradient, control init, z0 and the first delta.
+static void enqueue_solve_head(DpoCtx* c, double* X, const double* nbr,
+                               double tol, double Delta0, hipStream_t s) {
   const int n = c->n, d = c->d, r = c->r;
   const long total = c->total;
   const int gvec = (int)((total + 255) / 256);
-  // Fused control tails (CF_*): the tCG scalar decisions run in the
-  // last-arriving block of the producing reduction kernel instead of a
-  // dedicated single-wave kernel, removing 3 of 8 launches per tCG
-  // iteration. The ~4 us/launch dispatch latency floor is what bounds
-  // these small-agent solves (see profiles/), so launch count is the
-  // lever. An earlier attempt at this fusion showed trajectory scatter
-  // that was eventually root-caused to an LDS reuse race in
-  // block_reduce_atomic plus the hipGraph ordering bugs (both fixed);
-  // DPO_NO_CF=1 runs each tail as a standalone k_ctrl_tail launch.
-  static const bool no_cf = dpo_env_flag("DPO_NO_CF");
   fence_wait(c, F_SOLVE_IN, s);  // first node: block until inputs ready
   if (nbr) ctx_assemble_g(c, nbr, s);
   dzero(c->ctrl, CTRL_SIZE, s);
 
   // gradient phase: one fused kernel computes Q@X + G, projects at X
   // and accumulates <P,P> / <QX+G,X> (was spmm + proj_dots — the
-  // two-kernel split re-read the full iterate from HBM)
-  launch_hess_fused<0>(c->q_rp, c->q_ci, c->q_vals, X, X, c->Gt,
-                       c->grad, nullptr, c->ctrl, n, d, r,
-                       C_DOT1, C_DOT0, -1, s,
-                       c->Gt ? C_DOT2 : -1);  // <G,X> folded in
-  hipLaunchKernelGGL(k_axpby, dim3(gvec), dim3(256), 0, s,
-                     c->grad, (const double*)nullptr, 1.0, 0.0, c->rvec,
-                     total);
+  // two-kernel split re-read the full iterate from HBM). It writes the
+  // gradient to grad and to rvec (the tCG residual starts as the
+  // gradient) and clears z for the z0 dense apply.
+  launch_hess_fused<0, CF_NONE, 1>(
+      c->q_rp, c->q_ci, c->q_vals, X, X, c->Gt, c->grad, nullptr,
+      c->ctrl, n, d, r, C_DOT1, C_DOT0, -1, s,
+      c->Gt ? C_DOT2 : -1,  // <G,X> folded in
+      c->rvec, ctx_prezero_z(c));
   hipLaunchKernelGGL(k_ctrl_init, dim3(1), dim3(64), 0, s, c->ctrl, tol,
                      Delta0, 1.0, 0.1);
   // z0
-  if (no_cf) {
+  if (solve_no_cf()) {
     ctx_precond(c, c->rvec, c->z, s);
     launch_proj_dots(X, c->z, nullptr, c->z, c->rvec, c->ctrl, n, d, r,
                      C_DOT0, -1, ST_RUN, s);
@@ -2149,8 +2233,19 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
   }
   hipLaunchKernelGGL(k_tcg_delta, dim3(gvec), dim3(256), 0, s,
                      c->delta, c->z, c->ctrl, total);
+}
 
-  for (int j = 0; j < c->max_inner; ++j) {
+// `count` tCG iterations. Position-independent: every kernel reads the
+// iteration index from the control block (C_ITER) and is a no-op unless
+// the status is ST_RUN.
+static void enqueue_tcg_iters(DpoCtx* c, double* X, int count,
+                              hipStream_t s) {
+  const int n = c->n, d = c->d, r = c->r;
+  const long total = c->total;
+  const int gvec = (int)((total + 255) / 256);
+  const bool no_cf = solve_no_cf();
+  double* zero_z = ctx_prezero_z(c);  // cleared for the next dense apply
+  for (int j = 0; j < count; ++j) {
     if (no_cf) {
       launch_hess_fused<0>(c->q_rp, c->q_ci, c->q_vals, c->delta, X,
                            nullptr, c->Hd, c->delta, c->ctrl, n, d, r,
@@ -2160,7 +2255,7 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
                          dim3(blocks_for((total + 3) / 4, 256)),
                          dim3(256), 0, s, c->eta, c->rvec, c->delta,
                          c->Hd, c->eta_snap, c->delta_snap, c->ctrl,
-                         total);
+                         total, zero_z);
       launch_ctrl_tail<CF_RR>(c->ctrl, s);
     } else {
       launch_hess_fused<0, CF_ALPHA>(
@@ -2170,7 +2265,7 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
                          dim3(blocks_for((total + 3) / 4, 256)),
                          dim3(256), 0, s, c->eta, c->rvec, c->delta,
                          c->Hd, c->eta_snap, c->delta_snap, c->ctrl,
-                         total);
+                         total, zero_z);
     }
     if (no_cf) {
       ctx_precond(c, c->rvec, c->z, s);
@@ -2183,8 +2278,17 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
     hipLaunchKernelGGL(k_tcg_delta, dim3(gvec), dim3(256), 0, s,
                        c->delta, c->z, c->ctrl, total);
   }
-  hipLaunchKernelGGL(k_ctrl_tcg_end, dim3(1), dim3(64), 0, s, c->ctrl);
-  // first candidate attempt is part of the fixed sequence
+}
+
+// Tail: first candidate + acceptance test, control block to the host.
+// Every kernel but the copy is guarded by ST_TCG_STOP, so behind a
+// segment that left tCG running the tail is a no-op and the host reads
+// ST_RUN.
+static void enqueue_solve_tail(DpoCtx* c, double* X, double accept_rho,
+                               hipStream_t s) {
+  const int n = c->n, d = c->d, r = c->r;
+  const long total = c->total;
+  const int gvec = (int)((total + 255) / 256);
   hipLaunchKernelGGL(k_ctrl_candidate, dim3(1), dim3(64), 0, s, c->ctrl);
   hipLaunchKernelGGL(k_form_step, dim3(gvec), dim3(256), 0, s,
                      c->step, c->eta, c->eta_snap, c->delta_snap,
@@ -2201,6 +2305,29 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
   fence_signal(c, F_SOLVE_OUT, s);  // last node: mark sequence complete
 }
 
+// Primary sequence: head + `iters` tCG iterations + tail. The max_inner
+// cap (k_ctrl_tcg_end) belongs to the segment that holds the last
+// iteration.
+static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
+                               double tol, double Delta0,
+                               double accept_rho, int iters,
+                               hipStream_t s) {
+  enqueue_solve_head(c, X, nbr, tol, Delta0, s);
+  enqueue_tcg_iters(c, X, iters, s);
+  if (iters >= c->max_inner)
+    hipLaunchKernelGGL(k_ctrl_tcg_end, dim3(1), dim3(64), 0, s, c->ctrl);
+  enqueue_solve_tail(c, X, accept_rho, s);
+}
+
+// Continuation sequence: the iterations after the primary's `done`.
+static void enqueue_solve_cont(DpoCtx* c, double* X, double accept_rho,
+                               int done, hipStream_t s) {
+  fence_wait(c, F_SOLVE_IN, s);
+  enqueue_tcg_iters(c, X, c->max_inner - done, s);
+  hipLaunchKernelGGL(k_ctrl_tcg_end, dim3(1), dim3(64), 0, s, c->ctrl);
+  enqueue_solve_tail(c, X, accept_rho, s);
+}
+
 // Full RBCD local solve in place on X. stats_out (host, >= 8 doubles):
 // [status, f_init, gn_init, f_opt, gn_opt, rho, shrink_count, iters]
 // nbr != null: assemble G from the packed neighbor buffer first; the
@@ -2213,27 +2340,55 @@ static bool solve_presync(DpoCtx* c, double* X, const double* nbr,
                           double tol, double Delta0, double accept_rho,
                           hipStream_t s) {
   static const bool no_graph = dpo_env_flag("DPO_NO_SOLVE_GRAPH");
+  // the eager paths enqueue every iteration: nothing is saved by
+  // segmenting a sequence that is not replayed
   if (no_graph) {
     // fully async eager enqueue; callers sync (finish / impl)
-    enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, s);
+    enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, c->max_inner,
+                       s);
     fence_wait(c, F_SOLVE_OUT, s);
     return true;
   }
   const void* key[4] = {X, nbr, (const void*)(intptr_t)(tol * 1e9),
                         (const void*)(intptr_t)Delta0};
+  const int seg = solve_segment(c);
   const bool launched = graph_cache_launch(
       c->solve_graph, key, c->cap_stream, s, [&](hipStream_t cs) {
-        enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, cs);
+        enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, seg, cs);
       });
   if (!launched) {
     // capture unavailable: run eagerly on the caller's stream
-    enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, s);
+    enqueue_solve_body(c, X, nbr, tol, Delta0, accept_rho, c->max_inner,
+                       s);
     fence_wait(c, F_SOLVE_OUT, s);
     DPO_CHECK(hipStreamSynchronize(s));
     return false;
   }
   // eager wait pins downstream stream work (and host syncs) to the
   // graph's actual completion even if the launch misordered
+  fence_wait(c, F_SOLVE_OUT, s);
+  return true;
+}
+
+// After the primary sequence has completed on s (ctrl_host is valid):
+// if it left tCG running — only a primary graph shorter than max_inner
+// can — launch the continuation graph on s, fenced like the primary,
+// and return true; the caller syncs s again before solve_postsync.
+static bool solve_continue(DpoCtx* c, double* X, const double* nbr,
+                           double tol, double Delta0, double accept_rho,
+                           hipStream_t s) {
+  if ((int)c->ctrl_host[C_STATUS] != ST_RUN) return false;
+  const int seg = solve_segment(c);
+  if (seg >= c->max_inner) return false;
+  c->n_conts++;
+  fence_signal(c, F_SOLVE_IN, s);
+  const void* key[4] = {X, nbr, (const void*)(intptr_t)(tol * 1e9),
+                        (const void*)(intptr_t)Delta0};
+  const bool launched = graph_cache_launch(
+      c->cont_graph, key, c->cap_stream, s, [&](hipStream_t cs) {
+        enqueue_solve_cont(c, X, accept_rho, seg, cs);
+      });
+  if (!launched) enqueue_solve_cont(c, X, accept_rho, seg, s);
   fence_wait(c, F_SOLVE_OUT, s);
   return true;
 }
@@ -2296,6 +2451,11 @@ static int solve_postsync(DpoCtx* c, double* X, double accept_rho,
     DPO_CHECK(hipStreamSynchronize(s));
     gn_opt = sqrt(c->ctrl_host[C_DOT1]);
   }
+  c->n_solves++;
+  {
+    const int hlen = (int)c->ctrl_host[C_HLEN];
+    c->hlen_hist[hlen < 0 ? 0 : (hlen > MAX_TCG ? MAX_TCG : hlen)]++;
+  }
   if (stats_out) {
     stats_out[0] = status;
     stats_out[1] = f_init;
@@ -2316,6 +2476,8 @@ static int rbcd_solve_impl(DpoCtx* c, double* X, const double* nbr,
   fence_signal(c, F_SOLVE_IN, s);
   bool async = solve_presync(c, X, nbr, tol, Delta0, accept_rho, s);
   if (async) DPO_CHECK(hipStreamSynchronize(s));
+  if (solve_continue(c, X, nbr, tol, Delta0, accept_rho, s))
+    DPO_CHECK(hipStreamSynchronize(s));
   return solve_postsync(c, X, accept_rho, max_shrink, compute_final_gn,
                         stats_out, s);
 }
@@ -2351,20 +2513,56 @@ void dpo_round_solve_async(void* h, double* X, const double* nbr,
   fence_signal(c, F_SOLVE_IN, js);
   solve_presync(c, X, nbr, tol, Delta0, accept_rho, c->exec_stream);
   c->pend_X = X;
+  c->pend_nbr = nbr;
   c->pend_tol = tol;
   c->pend_Delta0 = Delta0;
   c->pend_rho = accept_rho;
 }
 
-int dpo_round_solve_finish(void* h, int max_shrink, double* stats_out,
-                           void* join_stream) {
-  DpoCtx* c = (DpoCtx*)h;
+// Finishing an async solve takes two steps, so that a group can run
+// step 1 for every agent before step 2 for any: one agent's
+// continuation then overlaps the others' instead of serialising them.
+// Step 1: wait for the primary sequence; launch the continuation if
+// tCG is still running. Returns whether it did.
+static bool round_finish_primary(DpoCtx* c) {
   DPO_CHECK(hipStreamSynchronize(c->exec_stream));
+  return solve_continue(c, c->pend_X, c->pend_nbr, c->pend_tol,
+                        c->pend_Delta0, c->pend_rho, c->exec_stream);
+}
+
+// Step 2: wait for the continuation (if any), post-process, join.
+static int round_finish_post(DpoCtx* c, bool continued, int max_shrink,
+                             double* stats_out, hipStream_t js) {
+  if (continued) DPO_CHECK(hipStreamSynchronize(c->exec_stream));
   int st = solve_postsync(c, c->pend_X, c->pend_rho, max_shrink, 0,
                           stats_out, c->exec_stream);
   DPO_CHECK(hipEventRecord(c->done_event, c->exec_stream));
-  DPO_CHECK(hipStreamWaitEvent((hipStream_t)join_stream, c->done_event, 0));
+  DPO_CHECK(hipStreamWaitEvent(js, c->done_event, 0));
   return st;
+}
+
+int dpo_round_solve_finish(void* h, int max_shrink, double* stats_out,
+                           void* join_stream) {
+  DpoCtx* c = (DpoCtx*)h;
+  const bool continued = round_finish_primary(c);
+  return round_finish_post(c, continued, max_shrink, stats_out,
+                           (hipStream_t)join_stream);
+}
+
+// out[0] = solves, out[1] = continuation launches, out[2 + h] = solves
+// that ended with C_HLEN == h (h = 0 .. MAX_TCG). Writes at most `cap`
+// entries; returns the full length.
+// tCG iterations in the primary solve graph of this context, for the
+// problem currently bound (DPO_TCG_SEG resolved); == max_inner: one graph.
+int dpo_tcg_segment(void* h) { return solve_segment((DpoCtx*)h); }
+
+int dpo_ctx_counters(void* h, long* out, int cap) {
+  DpoCtx* c = (DpoCtx*)h;
+  const int len = 2 + MAX_TCG + 1;
+  for (int i = 0; i < len && i < cap; ++i)
+    out[i] = (i == 0) ? c->n_solves
+           : (i == 1) ? c->n_conts : c->hlen_hist[i - 2];
+  return len;
 }
 
 void dpo_round_eval_async(void* h, const double* X, const double* nbr,
@@ -2594,9 +2792,20 @@ void dpo_group_solve_start(void* g, const int* ids, int k, double tol,
 void dpo_group_solve_finish(void* g, const int* ids, int k,
                             int max_shrink, void* join_stream) {
   DpoGroup* gr = (DpoGroup*)g;
-  for (int i = 0; i < k; ++i)
-    dpo_round_solve_finish(gr->cs[ids[i]], max_shrink, nullptr,
-                           join_stream);
+  bool continued[256];  // dpo_group_create caps a group at 256 agents
+  // pass 1: an agent that needs no continuation is finished at once, as
+  // before; one that does only gets its continuation launched
+  for (int i = 0; i < k && i < 256; ++i) {
+    continued[i] = round_finish_primary(gr->cs[ids[i]]);
+    if (!continued[i])
+      round_finish_post(gr->cs[ids[i]], false, max_shrink, nullptr,
+                        (hipStream_t)join_stream);
+  }
+  // pass 2: the continued agents
+  for (int i = 0; i < k && i < 256; ++i)
+    if (continued[i])
+      round_finish_post(gr->cs[ids[i]], true, max_shrink, nullptr,
+                        (hipStream_t)join_stream);
 }
 
 // Fan-out evaluation of EVERY agent in the group into its eval3

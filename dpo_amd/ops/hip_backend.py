@@ -67,6 +67,10 @@ _lib.dpo_round_solve_async.argtypes = [_c, _c, _c, _d, _d, _d, _c]
 _lib.dpo_round_solve_finish.restype = _i
 _lib.dpo_round_solve_finish.argtypes = [
     _c, _i, ctypes.POINTER(ctypes.c_double), _c]
+_lib.dpo_tcg_segment.restype = _i
+_lib.dpo_tcg_segment.argtypes = [_c]
+_lib.dpo_ctx_counters.restype = _i
+_lib.dpo_ctx_counters.argtypes = [_c, ctypes.POINTER(ctypes.c_long), _i]
 _lib.dpo_round_eval_async.argtypes = [_c, _c, _c, _c, _c]
 _lib.dpo_eval_join.argtypes = [_c, _c]
 _lib.dpo_gnc_weights.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c, _c,
@@ -314,6 +318,22 @@ class DeviceSolver:
             "rho": st[5],
             "shrinks": int(st[6]),
         }
+
+    def tcg_segment(self) -> int:
+        """tCG iterations held by the primary solve graph for the problem
+        currently bound (DPO_TCG_SEG resolved); == max_inner means one
+        graph."""
+        return int(_lib.dpo_tcg_segment(self.handle))
+
+    def counters(self) -> dict:
+        """Host-side solve statistics of this context: solves finished,
+        continuation-graph launches (DPO_TCG_SEG), and the histogram of
+        tCG iterations per solve (index = Krylov history length)."""
+        buf = (ctypes.c_long * (MAX_TCG + 3))()
+        n = _lib.dpo_ctx_counters(self.handle, buf, len(buf))
+        assert n == len(buf)
+        return {"solves": int(buf[0]), "continuations": int(buf[1]),
+                "hlen_hist": [int(v) for v in buf[2:]]}
 
     def eval_terms(self, problem, X: Tensor) -> Tensor:
         """Device 3-vector [f(X), 0.5<X,G>, ||rgrad||^2]; no host sync."""
