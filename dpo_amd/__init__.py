@@ -31,3 +31,10 @@ from .types import (  # noqa: F401
     OptAlgorithm,
 )
 from .agent import PGOAgent  # noqa: F401
+from .certify import (  # noqa: F401
+    CertificateResult,
+    CertificateStatus,
+    certificate_operator,
+    certify_solution,
+    escape_direction,
+)

@@ -1058,6 +1058,24 @@ class DistributedRBCDDriver:
             buf.numpy().transpose(1, 0, 2).reshape(self.d,
                                                    self.n_global * dh))
 
+    def gather_lifted_iterate(self):
+        """Global lifted iterate Xt (n_global (d+1), r) on rank 0, pose
+        blocks in the `pose_to_index` order — the unrounded input of
+        `dpo_amd.certify.certify_solution`. Returns None on other
+        ranks."""
+        import torch
+        dh = self.dh
+        buf = torch.zeros(self.n_global, dh, self.r, dtype=torch.float64)
+        for rb, a in self.local_agents.items():
+            Xa = a.X.detach().cpu().view(a.n, dh, self.r)
+            idx = torch.tensor([self.pose_to_index[(rb, i)]
+                                for i in range(a.n)], dtype=torch.int64)
+            buf.index_copy_(0, idx, Xa)
+        self.comm.all_reduce_sum_(buf.view(-1))
+        if self.comm.rank != 0:
+            return None
+        return buf.view(self.n_global * dh, self.r)
+
     def _sync_anchor(self):
         import torch
         blk = self.dh * self.r

@@ -106,3 +106,90 @@ def sym_block_diag(Q: Tensor, d: int, reg: float = 0.1) -> Tensor:
     blocks.index_put_((bi[mask], br, bc), val[mask], accumulate=True)
     blocks += reg * torch.eye(dh, dtype=Q.dtype, device=Q.device)
     return blocks
+
+
+# ---------------------------------------------------------------------
+# Optimality certificate: S = Q - Lambda(X), Lanczos with full
+# reorthogonalisation (docs/DESIGN.md §14). Q is a BSRMatrix; the CPU
+# path multiplies with its scalar CSR mirror.
+# ---------------------------------------------------------------------
+# control array: [flag, completed steps, breakdown threshold, -,
+#                 alpha[0..m), beta[0..m)]
+CERT_FLAG, CERT_COUNT, CERT_TOL, CERT_HDR = 0, 1, 2, 4
+
+# (d, r) shapes the HIP extension compiles (DPO_FOREACH_DR)
+CERT_SHAPES = {2: range(2, 7), 3: range(3, 9)}
+
+
+def cert_check_shape(d: int, r: Optional[int]) -> None:
+    """Raise ValueError for a (d, r) outside the compiled shape table
+    (r = None checks d alone)."""
+    if d not in CERT_SHAPES or (r is not None and r not in CERT_SHAPES[d]):
+        raise ValueError(
+            f"unsupported (d={d}, r={r}): compiled shapes are d=2 with "
+            "r in 2..6 and d=3 with r in 3..8")
+
+
+def cert_lambda(Q, Xt: Tensor, d: int) -> Tuple[Tensor, Tensor]:
+    """Lambda blocks (n, d, d), Lambda_i = sym(QX_i X_i^T) on the rotation
+    rows, and the 1-element tensor ||Q Xt - Lambda Xt||_F^2."""
+    QX = torch.sparse.mm(Q.to_scalar_csr(), Xt)
+    Xb = _pose_view(Xt, d)
+    Gb = _pose_view(QX, d).clone()
+    Yt = Xb[:, :d, :]
+    A = torch.bmm(Gb[:, :d, :], Yt.transpose(1, 2))
+    lam = 0.5 * (A + A.transpose(1, 2))
+    Gb[:, :d, :] -= torch.bmm(lam, Yt)
+    return lam.contiguous(), (Gb * Gb).sum().reshape(1)
+
+
+def _cert_s_apply(csr: Tensor, lam: Tensor, v: Tensor) -> Tensor:
+    n, d = lam.shape[0], lam.shape[1]
+    w = torch.sparse.mm(csr, v[:, None])[:, 0]
+    wb = w.view(n, d + 1)
+    wb[:, :d] -= torch.bmm(lam, v.view(n, d + 1)[:, :d, None])[:, :, 0]
+    return w
+
+
+def cert_apply(Q, lam: Tensor, v: Tensor, v_prev: Optional[Tensor] = None,
+               beta_prev: float = 0.0) -> Tuple[Tensor, Tensor]:
+    """w = (Q - Lambda) v - beta_prev * v_prev and alpha = <v, w>."""
+    w = _cert_s_apply(Q.to_scalar_csr(), lam, v)
+    if v_prev is not None:
+        w -= beta_prev * v_prev
+    return w, torch.dot(v, w).reshape(1)
+
+
+def cert_lanczos_steps(Q, lam: Tensor, V: Tensor, ctl: Tensor,
+                       first_step: int, nsteps: int) -> None:
+    """Lanczos steps first_step .. first_step + nsteps - 1 in place.
+
+    V is the (m + 1, N) basis (row j = v_j, row 0 set by the caller).
+    Step j forms w = S v_j - beta_{j-1} v_{j-1}, alpha_j = <v_j, w>,
+    orthogonalises w against v_0..v_j twice (CGS2), then beta_j = ||w||
+    and v_{j+1} = w / beta_j. When beta_j falls below ctl[CERT_TOL] the
+    flag is set, beta_j is recorded as 0 and every later step is a
+    no-op, so nothing divides by a vanished beta."""
+    m = V.shape[0] - 1
+    assert ctl.numel() == CERT_HDR + 2 * m
+    assert 0 <= first_step and first_step + nsteps <= m
+    csr = Q.to_scalar_csr()
+    tol = float(ctl[CERT_TOL])
+    for j in range(first_step, first_step + nsteps):
+        if float(ctl[CERT_FLAG]) != 0.0:
+            return
+        w = _cert_s_apply(csr, lam, V[j])
+        if j > 0:
+            w -= ctl[CERT_HDR + m + j - 1] * V[j - 1]
+        ctl[CERT_HDR + j] = torch.dot(V[j], w)
+        B = V[:j + 1]
+        for _ in range(2):
+            w -= B.T @ (B @ w)
+        beta = float(torch.linalg.norm(w))
+        ok = beta >= tol and beta > 0.0
+        ctl[CERT_HDR + m + j] = beta if ok else 0.0
+        ctl[CERT_COUNT] = j + 1
+        if not ok:
+            ctl[CERT_FLAG] = 1.0
+            return
+        V[j + 1] = w / beta

@@ -2830,3 +2830,347 @@ void dpo_group_eval(void* g, double* out_dev, long row_stride,
 }
 
 }  // extern "C"
+
+// =====================================================================
+// Optimality certificate: S = Q - Lambda(X) and Lanczos with full
+// reorthogonalisation (docs/DESIGN.md §14). Purely additive: none of the
+// solve/eval kernels above is used or changed, except that Q @ X comes
+// from k_bsr_spmm.
+//
+// Reductions are run-to-run deterministic: every block
+// reduces in a fixed shuffle/LDS order and stores ONE partial into a
+// per-block slot; the consuming kernel (always a later launch, so the
+// kernel boundary publishes the slots) sums the <= CERT_MAX_PART
+// partials in the same fixed order. No floating-point atomics.
+//
+// Control array `cc` (fp64): flag, completed-step count, breakdown
+// threshold, then alpha[m] and beta[m]. Once the flag is set every
+// later kernel of the enqueued batch returns at once (the guard idiom
+// of the solve kernels), so no step divides by a vanished beta.
+// =====================================================================
+enum CertSlot {
+  CC_FLAG = 0,   // != 0: Krylov space exhausted (breakdown)
+  CC_COUNT = 1,  // completed Lanczos steps (alpha_j, beta_j valid)
+  CC_TOL = 2,    // absolute breakdown threshold on beta
+  CC_HDR = 4,    // alpha[j] at CC_HDR + j, beta[j] at CC_HDR + m + j
+};
+#define CERT_MAX_PART 256
+#define CERT_BS 256
+
+static inline int cert_grid(long total) {
+  const int g = blocks_for(total, CERT_BS);
+  return g < CERT_MAX_PART ? g : CERT_MAX_PART;
+}
+
+__device__ __forceinline__ bool cert_off(const double* cc) {
+  return cc != nullptr && cc[CC_FLAG] != 0.0;
+}
+
+// Fixed-order block sum (blockDim.x == CERT_BS); every thread returns
+// the same value.
+__device__ __forceinline__ double cert_block_sum(double v) {
+  __shared__ double sh[CERT_BS / 64];
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = sh[0];
+  #pragma unroll
+  for (int w = 1; w < CERT_BS / 64; ++w) s += sh[w];
+  __syncthreads();  // sh is reused by the next reduction in this kernel
+  return s;
+}
+
+__device__ __forceinline__ double cert_sum_partials(const double* part,
+                                                    int npart) {
+  const int t = threadIdx.x;
+  return cert_block_sum(t < npart ? part[t] : 0.0);
+}
+
+// out[0] = sum of the per-block partials (single block)
+__global__ void k_cert_reduce(const double* __restrict__ part, int npart,
+                              double* __restrict__ out) {
+  const double s = cert_sum_partials(part, npart);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
+// Lambda blocks and the criticality residual. One thread per pose:
+//   Lambda_i = sym(QX_i X_i^T) on the d rotation rows (d x d),
+//   part[b]  = block partial of ||QX - Lambda X||_F^2 (the translation
+//              row of Lambda is zero, so its rows contribute QX^2).
+template <int D, int R>
+__global__ void k_cert_lambda(const double* __restrict__ X,
+                              const double* __restrict__ QX,
+                              double* __restrict__ lam,
+                              double* __restrict__ part, int n) {
+  constexpr int dh = D + 1;
+  double res = 0.0;
+  for (int i = blockIdx.x * CERT_BS + threadIdx.x; i < n;
+       i += gridDim.x * CERT_BS) {
+    const double* Xi = X + (size_t)i * dh * R;
+    const double* Gi = QX + (size_t)i * dh * R;
+    double Y[D][R], G[D][R];
+    #pragma unroll
+    for (int a = 0; a < D; ++a)
+      #pragma unroll
+      for (int k = 0; k < R; ++k) {
+        Y[a][k] = Xi[a * R + k];
+        G[a][k] = Gi[a * R + k];
+      }
+    double L[D][D];
+    #pragma unroll
+    for (int a = 0; a < D; ++a)
+      #pragma unroll
+      for (int b = a; b < D; ++b) {
+        double s = 0.0;
+        #pragma unroll
+        for (int k = 0; k < R; ++k)
+          s = fma(G[a][k], Y[b][k], fma(G[b][k], Y[a][k], s));
+        s *= 0.5;
+        L[a][b] = s;
+        L[b][a] = s;
+      }
+    #pragma unroll
+    for (int a = 0; a < D; ++a)
+      #pragma unroll
+      for (int b = 0; b < D; ++b)
+        lam[(size_t)i * D * D + a * D + b] = L[a][b];
+    #pragma unroll
+    for (int a = 0; a < D; ++a)
+      #pragma unroll
+      for (int k = 0; k < R; ++k) {
+        double g = G[a][k];
+        #pragma unroll
+        for (int b = 0; b < D; ++b) g = fma(-L[a][b], Y[b][k], g);
+        res = fma(g, g, res);
+      }
+    #pragma unroll
+    for (int k = 0; k < R; ++k) {
+      const double g = Gi[D * R + k];
+      res = fma(g, g, res);
+    }
+  }
+  const double s = cert_block_sum(res);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// One fused Lanczos step on a single vector, one thread per scalar row
+// (BSR traversal of k_bsr_spmm with r = 1):
+//   w_i = sum_j Q_ij v_j - Lambda_i v_i - beta_prev * vprev_i
+//   part[b] = block partial of alpha = <v, w>
+// beta_prev is read from a device slot (nullptr: first step, 0).
+template <int D>
+__global__ void k_cert_apply(const int* __restrict__ row_ptr,
+                             const int* __restrict__ col_idx,
+                             const double* __restrict__ vals,
+                             const double* __restrict__ lam,
+                             const double* __restrict__ v,
+                             const double* __restrict__ vprev,
+                             const double* __restrict__ beta_prev,
+                             double* __restrict__ w,
+                             double* __restrict__ part, int n,
+                             const double* __restrict__ cc) {
+  if (cert_off(cc)) return;
+  constexpr int DH = D + 1;
+  const long N = (long)n * DH;
+  const double beta = (beta_prev && vprev) ? beta_prev[0] : 0.0;
+  double dot = 0.0;
+  for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+       row += (long)gridDim.x * CERT_BS) {
+    const int i = (int)(row / DH);
+    const int c = (int)(row % DH);
+    const int s = row_ptr[i], e = row_ptr[i + 1];
+    double acc = 0.0;
+    for (int p = s; p < e; ++p) {
+      const double* B = vals + (size_t)p * DH * DH + c * DH;
+      const double* vj = v + (size_t)col_idx[p] * DH;
+      #pragma unroll
+      for (int cc2 = 0; cc2 < DH; ++cc2) acc = fma(B[cc2], vj[cc2], acc);
+    }
+    if (c < D) {
+      const double* Li = lam + (size_t)i * D * D + c * D;
+      const double* vi = v + (size_t)i * DH;
+      #pragma unroll
+      for (int b = 0; b < D; ++b) acc = fma(-Li[b], vi[b], acc);
+    }
+    if (vprev) acc = fma(-beta, vprev[row], acc);
+    w[row] = acc;
+    dot = fma(v[row], acc, dot);
+  }
+  const double sdot = cert_block_sum(dot);
+  if (threadIdx.x == 0) part[blockIdx.x] = sdot;
+}
+
+// c = V^T w against the stored basis (column-major, ncols columns of
+// length N): one workgroup per basis column. Block 0 of the first pass
+// also finalises alpha from k_cert_apply's partials.
+__global__ void k_cert_gram(const double* __restrict__ V,
+                            const double* __restrict__ w,
+                            double* __restrict__ c, long N,
+                            const double* __restrict__ cc,
+                            const double* __restrict__ part, int npart,
+                            double* __restrict__ alpha_out) {
+  if (cert_off(cc)) return;
+  const double* Vk = V + (size_t)blockIdx.x * N;
+  double dot = 0.0;
+  for (long row = threadIdx.x; row < N; row += CERT_BS)
+    dot = fma(Vk[row], w[row], dot);
+  const double s = cert_block_sum(dot);
+  if (threadIdx.x == 0) c[blockIdx.x] = s;
+  if (alpha_out != nullptr && blockIdx.x == 0) {
+    const double a = cert_sum_partials(part, npart);
+    if (threadIdx.x == 0) alpha_out[0] = a;
+  }
+}
+
+// w -= V c; with part != nullptr also the block partials of ||w||^2.
+__global__ void k_cert_sub(const double* __restrict__ V,
+                           const double* __restrict__ c,
+                           double* __restrict__ w, int ncols, long N,
+                           const double* __restrict__ cc,
+                           double* __restrict__ part) {
+  if (cert_off(cc)) return;
+  double nrm = 0.0;
+  for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+       row += (long)gridDim.x * CERT_BS) {
+    double acc = w[row];
+    for (int k = 0; k < ncols; ++k)
+      acc = fma(-c[k], V[(size_t)k * N + row], acc);
+    w[row] = acc;
+    nrm = fma(acc, acc, nrm);
+  }
+  if (part != nullptr) {
+    const double s = cert_block_sum(nrm);
+    if (threadIdx.x == 0) part[blockIdx.x] = s;
+  }
+}
+
+// beta_j = ||w||; breakdown test; v_{j+1} = w / beta_j. Every block sums
+// the same partials in the same order, so all blocks take the same
+// branch. Block 0 records beta_j and the step count and raises the flag;
+// a block that already sees the flag raised by block 0 of this launch
+// returns without normalising, which is what the breakdown branch does.
+__global__ void k_cert_norm(const double* __restrict__ w,
+                            double* __restrict__ vnext, long N,
+                            double* __restrict__ cc,
+                            const double* __restrict__ part, int npart,
+                            int j, int m) {
+  // one flag read per block: block 0 of this launch may be raising it
+  // right now, and a block must not split over the two values
+  __shared__ int off;
+  if (threadIdx.x == 0) off = cert_off(cc) ? 1 : 0;
+  __syncthreads();
+  if (off) return;
+  const double beta = sqrt(cert_sum_partials(part, npart));
+  const bool ok = beta >= cc[CC_TOL] && beta > 0.0;  // false for NaN too
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    cc[CC_HDR + m + j] = ok ? beta : 0.0;
+    cc[CC_COUNT] = (double)(j + 1);
+    if (!ok) cc[CC_FLAG] = 1.0;
+  }
+  if (!ok) return;
+  const double inv = 1.0 / beta;
+  for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+       row += (long)gridDim.x * CERT_BS)
+    vnext[row] = w[row] * inv;
+}
+
+static void launch_cert_lambda(const double* X, const double* QX,
+                               double* lam, double* part, int n, int d,
+                               int r, hipStream_t s) {
+#define CASE_CL(D, R) \
+  if (d == D && r == R) { \
+    hipLaunchKernelGGL((k_cert_lambda<D, R>), dim3(cert_grid(n)), \
+                       dim3(CERT_BS), 0, s, X, QX, lam, part, n); \
+    return; \
+  }
+  DPO_FOREACH_DR(CASE_CL)
+#undef CASE_CL
+  dpo_bad_shape(d, r);
+}
+
+static void launch_cert_apply(const int* rp, const int* ci,
+                              const double* vals, const double* lam,
+                              const double* v, const double* vprev,
+                              const double* beta_prev, double* w,
+                              double* part, int n, int d, const double* cc,
+                              hipStream_t s) {
+  const int grid = cert_grid((long)n * (d + 1));
+  if (d == 2)
+    hipLaunchKernelGGL((k_cert_apply<2>), dim3(grid), dim3(CERT_BS), 0, s,
+                       rp, ci, vals, lam, v, vprev, beta_prev, w, part, n,
+                       cc);
+  else if (d == 3)
+    hipLaunchKernelGGL((k_cert_apply<3>), dim3(grid), dim3(CERT_BS), 0, s,
+                       rp, ci, vals, lam, v, vprev, beta_prev, w, part, n,
+                       cc);
+  else
+    dpo_bad_shape(d, -1);
+}
+
+extern "C" {
+
+// lam (n, d, d) and res_out[0] = ||QX - Lambda X||_F^2 from X and
+// QX = Q @ X (both (N, r)). part: CERT_MAX_PART scratch doubles.
+void dpo_cert_lambda(const double* X, const double* QX, double* lam,
+                     double* res_out, double* part, int n, int d, int r,
+                     void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  launch_cert_lambda(X, QX, lam, part, n, d, r, s);
+  hipLaunchKernelGGL(k_cert_reduce, dim3(1), dim3(CERT_BS), 0, s, part,
+                     cert_grid(n), res_out);
+}
+
+// Stand-alone operator application: w = S v - beta_prev[0] * vprev,
+// alpha_out[0] = <v, w>. vprev / beta_prev may be null.
+void dpo_cert_apply(const int* row_ptr, const int* col_idx,
+                    const double* vals, const double* lam, const double* v,
+                    const double* vprev, const double* beta_prev, double* w,
+                    double* alpha_out, double* part, int n, int d,
+                    void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  launch_cert_apply(row_ptr, col_idx, vals, lam, v, vprev, beta_prev, w,
+                    part, n, d, nullptr, s);
+  hipLaunchKernelGGL(k_cert_reduce, dim3(1), dim3(CERT_BS), 0, s, part,
+                     cert_grid((long)n * (d + 1)), alpha_out);
+}
+
+// Enqueue Lanczos steps first_step .. first_step + nsteps - 1 on the
+// stream, eagerly and with no host synchronisation. V holds m + 1
+// columns of length N (column j = v_j), cvec m + 1 doubles, part
+// CERT_MAX_PART doubles, cc CC_HDR + 2 m doubles. Step j reads columns
+// 0..j and writes column j + 1 <= m; steps at or past m are not enqueued.
+void dpo_cert_lanczos(const int* row_ptr, const int* col_idx,
+                      const double* vals, const double* lam, double* V,
+                      double* w, double* cvec, double* part, double* cc,
+                      int n, int d, int m, int first_step, int nsteps,
+                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long N = (long)n * (d + 1);
+  const int grid = cert_grid(N);
+  for (int j = first_step; j < first_step + nsteps && j < m; ++j) {
+    const double* vj = V + (size_t)j * N;
+    const double* vp = j > 0 ? V + (size_t)(j - 1) * N : nullptr;
+    const double* bp = j > 0 ? cc + CC_HDR + m + j - 1 : nullptr;
+    launch_cert_apply(row_ptr, col_idx, vals, lam, vj, vp, bp, w, part, n,
+                      d, cc, s);
+    // CGS2: two classical Gram-Schmidt passes against columns 0..j
+    for (int pass = 0; pass < 2; ++pass) {
+      hipLaunchKernelGGL(k_cert_gram, dim3(j + 1), dim3(CERT_BS), 0, s,
+                         (const double*)V, (const double*)w, cvec, N,
+                         (const double*)cc, (const double*)part, grid,
+                         pass == 0 ? cc + CC_HDR + j : nullptr);
+      hipLaunchKernelGGL(k_cert_sub, dim3(grid), dim3(CERT_BS), 0, s,
+                         (const double*)V, (const double*)cvec, w, j + 1, N,
+                         (const double*)cc, pass == 1 ? part : nullptr);
+    }
+    hipLaunchKernelGGL(k_cert_norm, dim3(grid), dim3(CERT_BS), 0, s,
+                       (const double*)w, V + (size_t)(j + 1) * N, N, cc,
+                       (const double*)part, grid, j, m);
+  }
+}
+
+int dpo_cert_ctrl_header() { return CC_HDR; }
+int dpo_cert_max_part() { return CERT_MAX_PART; }
+
+}  // extern "C"

@@ -458,3 +458,90 @@ def gnc_weights(X: Tensor, nbr: Tensor, g: dict, weights: Tensor,
         _p(g["e2_nbr"]), _p(g["R"]), _p(g["t"]), _p(g["kappa"]),
         _p(g["tau"]), _p(g["upd"]), _p(g["widx"]), _p(weights),
         g["ne"], d, r, mu, barc_sq, _stream(X))
+
+
+# ---------------------------------------------------------------------
+# Optimality certificate (S = Q - Lambda(X), Lanczos with full
+# reorthogonalisation) — interface mirrors cpu_ref.cert_*
+# ---------------------------------------------------------------------
+_lib.dpo_cert_lambda.argtypes = [_c, _c, _c, _c, _c, _i, _i, _i, _c]
+_lib.dpo_cert_apply.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c, _c,
+                                _i, _i, _c]
+_lib.dpo_cert_lanczos.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c,
+                                  _i, _i, _i, _i, _i, _c]
+_lib.dpo_cert_ctrl_header.restype = _i
+_lib.dpo_cert_max_part.restype = _i
+
+from .cpu_ref import CERT_HDR, cert_check_shape  # noqa: E402
+
+assert _lib.dpo_cert_ctrl_header() == CERT_HDR
+_CERT_PART = _lib.dpo_cert_max_part()
+
+
+def _chk_q(Q, like: Tensor):
+    _chk(Q.vals)
+    _chk(Q.row_ptr, torch.int32)
+    _chk(Q.col_idx, torch.int32)
+    assert Q.vals.device == like.device
+
+
+def cert_lambda(Q, Xt: Tensor, d: int):
+    """Lambda blocks (n, d, d) of the certificate operator at Xt and the
+    1-element device tensor ||Q Xt - Lambda Xt||_F^2. No host sync."""
+    _chk(Xt); _chk_q(Q, Xt)
+    N, r = Xt.shape
+    n = N // (d + 1)
+    assert Q.n == n and Q.dh == d + 1 and N == n * (d + 1)
+    cert_check_shape(d, r)
+    QX = bsr_spmm(Q.row_ptr, Q.col_idx, Q.vals, n, d + 1, Xt)
+    lam = torch.empty(n, d, d, dtype=torch.float64, device=Xt.device)
+    res = torch.empty(1, dtype=torch.float64, device=Xt.device)
+    part = torch.empty(_CERT_PART, dtype=torch.float64, device=Xt.device)
+    _lib.dpo_cert_lambda(_p(Xt), _p(QX), _p(lam), _p(res), _p(part),
+                         n, d, r, _stream(Xt))
+    return lam, res
+
+
+def cert_apply(Q, lam: Tensor, v: Tensor, v_prev: Optional[Tensor] = None,
+               beta_prev: float = 0.0):
+    """w = (Q - Lambda) v - beta_prev * v_prev and the 1-element device
+    tensor alpha = <v, w> (one fused Lanczos operator application)."""
+    _chk(lam); _chk(v); _chk_q(Q, v)
+    n, d = lam.shape[0], lam.shape[1]
+    cert_check_shape(d, None)
+    assert Q.n == n and Q.dh == d + 1 and v.shape == (n * (d + 1),)
+    dev = v.device
+    beta = None
+    if v_prev is not None:
+        _chk(v_prev)
+        assert v_prev.shape == v.shape
+        beta = torch.tensor([beta_prev], dtype=torch.float64, device=dev)
+    w = torch.empty_like(v)
+    alpha = torch.empty(1, dtype=torch.float64, device=dev)
+    part = torch.empty(_CERT_PART, dtype=torch.float64, device=dev)
+    _lib.dpo_cert_apply(_p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals), _p(lam),
+                        _p(v), _p(v_prev), _p(beta), _p(w), _p(alpha),
+                        _p(part), n, d, _stream(v))
+    return w, alpha
+
+
+def cert_lanczos_steps(Q, lam: Tensor, V: Tensor, ctl: Tensor,
+                       first_step: int, nsteps: int) -> None:
+    """Enqueue Lanczos steps first_step .. first_step + nsteps - 1 with
+    no host synchronisation. V: (m + 1, N) basis, row j = v_j; ctl: the
+    (CERT_HDR + 2 m) control array (see cpu_ref.cert_lanczos_steps)."""
+    _chk(lam); _chk(V); _chk(ctl); _chk_q(Q, V)
+    n, d = lam.shape[0], lam.shape[1]
+    cert_check_shape(d, None)
+    m = V.shape[0] - 1
+    N = V.shape[1]
+    assert Q.n == n and Q.dh == d + 1 and N == n * (d + 1)
+    assert ctl.numel() == CERT_HDR + 2 * m
+    assert 0 <= first_step and nsteps >= 0 and first_step + nsteps <= m
+    dev = V.device
+    w = torch.empty(N, dtype=torch.float64, device=dev)
+    cvec = torch.empty(m + 1, dtype=torch.float64, device=dev)
+    part = torch.empty(_CERT_PART, dtype=torch.float64, device=dev)
+    _lib.dpo_cert_lanczos(_p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals),
+                          _p(lam), _p(V), _p(w), _p(cvec), _p(part),
+                          _p(ctl), n, d, m, first_step, nsteps, _stream(V))

@@ -34,6 +34,10 @@ def main():
                     help="write the final rounded global trajectory as "
                          "CSV (reference PartitionInitial.cpp:329-335)")
     ap.add_argument("--driver", default="dist", choices=["dist", "local"])
+    ap.add_argument("--certify", action="store_true",
+                    help="after the run, certify global optimality of the "
+                         "lifted iterate (min eigenvalue of Q - Lambda) and "
+                         "add the verdict to the JSON line")
     args = ap.parse_args()
 
     from dpo_amd.io_g2o import load_dataset
@@ -78,6 +82,18 @@ def main():
             lg = PGOLogger(os.path.dirname(args.dump_trajectory) or ".")
             lg.log_trajectory(meas[0].d, n, T,
                               os.path.basename(args.dump_trajectory))
+    if args.certify:
+        import torch
+        Xt = (drv.gather_lifted_iterate() if args.driver == "dist"
+              else drv._gather_global_x().reshape(-1, args.r))
+        if Xt is not None and rank == 0:
+            from dpo_amd.certify import certify_solution
+            t_cert = time.perf_counter()
+            cert = certify_solution(
+                meas, n, meas[0].d,
+                Xt.detach().to(torch.device(args.device)))
+            out.update(cert.as_dict())
+            out["certificate_s"] = time.perf_counter() - t_cert
     if rank == 0:
         print(json.dumps(out))
 

@@ -20,6 +20,10 @@ def main():
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--device", default="cpu")
     ap.add_argument("--dump-trajectory", default=None)
+    ap.add_argument("--certify", action="store_true",
+                    help="certify global optimality of the result (min "
+                         "eigenvalue of Q - Lambda) and add the verdict to "
+                         "the JSON line")
     args = ap.parse_args()
 
     from dpo_amd.agent import PGOAgent
@@ -47,6 +51,15 @@ def main():
         "grad_norm_opt": res.grad_norm_opt,
         "wall_s": wall,
     }
+    if args.certify:
+        import numpy as np
+        import torch
+        from dpo_amd.certify import certify_solution
+        # r = d: the lifted iterate is the trajectory itself, transposed
+        Xt = torch.from_numpy(np.ascontiguousarray(Topt.T)).to(
+            torch.device(args.device))
+        cert = certify_solution(meas, n, d, Xt)
+        out.update(cert.as_dict())
     print(json.dumps(out))
     if args.dump_trajectory:
         from dpo_amd.logger import PGOLogger
