@@ -2109,6 +2109,9 @@ void* dpo_ctx_create(int n, int d, int r, int max_inner) {
   DPO_CHECK(hipMalloc(&c->eta_snap, vb * (max_inner + 1)));
   DPO_CHECK(hipMalloc(&c->delta_snap, vb * (max_inner + 1)));
   DPO_CHECK(hipMalloc(&c->ctrl, CTRL_SIZE * sizeof(double)));
+  // hipMalloc does not clear: an evaluation before the first solve adds
+  // its dot products into C_DOT0..2 and relies on them starting at zero
+  DPO_CHECK(hipMemset(c->ctrl, 0, CTRL_SIZE * sizeof(double)));
   DPO_CHECK(hipMalloc(&c->G_buf, vb));
   // delta is consumed as `beta*delta - z` with beta == 0 on the first
   // tCG iteration: one-time zeroing keeps 0*garbage (possible NaN bit

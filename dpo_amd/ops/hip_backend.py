@@ -90,9 +90,12 @@ CTRL_SIZE = _lib.dpo_ctrl_size()
 
 # ctrl slots mirrored from dpo_ops.hip
 C_STATUS, C_FX, C_GN0SQ = 0, 1, 2
+C_RR, C_ZR, C_EPE, C_EPD, C_DPD, C_COEF, C_BETA, C_ITER, C_J = range(3, 12)
 C_RADIUS, C_FPROP, C_DM = 12, 13, 14
-C_GN1SQ, C_RHO = 20, 21
-C_DOT0, C_DOT1, C_DOT2 = 24, 25, 26
+C_JSTAR, C_TAUSTAR, C_USE_CURRENT, C_STOP_PENDING, C_BOUND = range(15, 20)
+C_GN1SQ, C_RHO, C_HLEN, C_SHRINKS = 20, 21, 22, 23
+C_DOT0, C_DOT1, C_DOT2, C_DOT3 = 24, 25, 26, 27
+C_HIST = 32  # z_r, d_Hd, e_Pe, e_Pd, d_Pd histories, MAX_TCG entries each
 ST_RUN, ST_TCG_STOP, ST_ACCEPTED, ST_GIVE_UP, ST_NO_UPDATE = range(5)
 MAX_TCG = 16
 GUARD_NONE, GUARD_RUN, GUARD_STOP = -1, ST_RUN, ST_TCG_STOP
@@ -110,6 +113,18 @@ def _chk(t: Tensor, dtype=torch.float64):
     assert t.is_cuda and t.dtype == dtype and t.is_contiguous()
 
 
+def _check_shape(d: Optional[int], r: Optional[int]) -> None:
+    """Raise ValueError unless (d, r) is a compiled kernel shape; the
+    native launchers abort the process on anything else. d = None
+    checks r alone (ops templated on r only)."""
+    from .cpu_ref import CERT_SHAPES, cert_check_shape
+    if d is not None:
+        cert_check_shape(d, r)
+    elif not any(r in rs for rs in CERT_SHAPES.values()):
+        raise ValueError(
+            f"unsupported r={r}: compiled shapes have r in 2..8")
+
+
 # ---------------------------------------------------------------------
 # op interface (mirrors cpu_ref)
 # ---------------------------------------------------------------------
@@ -117,6 +132,7 @@ def tangent_project(X: Tensor, V: Tensor, d: int) -> Tensor:
     _chk(X); _chk(V)
     n = X.shape[0] // (d + 1)
     r = X.shape[1]
+    _check_shape(d, r)
     out = torch.empty_like(V)
     _lib.dpo_proj_dots(_p(X), _p(V), None, _p(out), None, None,
                        n, d, r, -1, -1, 0, GUARD_NONE, _stream(X))
@@ -124,9 +140,21 @@ def tangent_project(X: Tensor, V: Tensor, d: int) -> Tensor:
 
 
 def stiefel_project(M: Tensor, d: int) -> Tensor:
+    """Per-pose polar factor of the d x r Stiefel block; translation
+    rows pass through.
+
+    Domain: the kernel iterates (Newton-Schulz, at most 40 steps) on the
+    d x d Gram matrix M M^T, so its error against the SVD polar factor
+    is about eps * cond(M)^2: 1e-12 at cond 1e2, 1e-8 at 1e4, 1e-4 at
+    1e6. Beyond cond(M) ~ 1e6 the result is silently not orthonormal. A
+    block whose Gram trace underflows (<= 1e-300) gives a zero block.
+    Retractions stay inside the domain: for X on the manifold and a
+    tangent eta the Gram matrix is I + eta eta^T, cond <= sqrt(1 +
+    ||eta||^2)."""
     _chk(M)
     n = M.shape[0] // (d + 1)
     r = M.shape[1]
+    _check_shape(d, r)
     out = torch.empty_like(M)
     _lib.dpo_polar_affine(_p(M), None, None, 1.0, 0.0, 0.0, _p(out),
                           n, d, r, None, GUARD_NONE, _stream(M))
@@ -137,6 +165,7 @@ def retract(X: Tensor, eta: Tensor, d: int) -> Tensor:
     _chk(X); _chk(eta)
     n = X.shape[0] // (d + 1)
     r = X.shape[1]
+    _check_shape(d, r)
     out = torch.empty_like(X)
     _lib.dpo_polar_affine(_p(X), _p(eta), None, 1.0, 1.0, 0.0, _p(out),
                           n, d, r, None, GUARD_NONE, _stream(X))
@@ -148,6 +177,7 @@ def polar_affine(A: Tensor, B: Optional[Tensor], C: Optional[Tensor],
     _chk(A)
     n = A.shape[0] // (d + 1)
     r = A.shape[1]
+    _check_shape(d, r)
     out = torch.empty_like(A)
     _lib.dpo_polar_affine(_p(A), _p(B), _p(C), ca, cb, cc, _p(out),
                           n, d, r, None, GUARD_NONE, _stream(A))
@@ -159,6 +189,10 @@ def bsr_spmm(row_ptr: Tensor, col_idx: Tensor, vals: Tensor, n: int,
              ctrl: Optional[Tensor] = None, guard: int = GUARD_NONE) -> Tensor:
     _chk(vals); _chk(X)
     r = X.shape[1]
+    # shapes outside the compiled table take the generic kernel, which
+    # needs at least one dh x r tile per 256-thread block
+    if dh < 1 or r < 1 or dh * r > 256:
+        raise ValueError(f"unsupported (dh={dh}, r={r}): needs dh*r <= 256")
     if out is None:
         out = torch.empty_like(X)
     _lib.dpo_bsr_spmm(_p(row_ptr), _p(col_idx), _p(vals), n, dh,
@@ -215,6 +249,7 @@ def precond_dense(Minv: Tensor, V: Tensor,
                   guard: int = GUARD_NONE) -> Tensor:
     _chk(Minv, torch.float32); _chk(V)
     N, r = V.shape
+    _check_shape(None, r)
     if out is None:
         out = torch.empty_like(V)
     _lib.dpo_precond_dense(_p(Minv), _p(V), _p(out), N, r, _p(ctrl), guard,
@@ -228,6 +263,8 @@ def precond_jacobi(L: Tensor, V: Tensor, dh: int,
                    guard: int = GUARD_NONE) -> Tensor:
     _chk(L); _chk(V)
     N, r = V.shape
+    if dh not in (3, 4):
+        raise ValueError(f"unsupported dh={dh}: compiled for dh in (3, 4)")
     n = N // dh
     if out is None:
         out = torch.empty_like(V)
@@ -257,6 +294,75 @@ def q_assemble(vals: Tensor, blocks: Tensor, slots: Tensor, edge_of: Tensor,
 
 
 # ---------------------------------------------------------------------
+# tCG vector ops. Coefficients, the iteration index and the guard status
+# are read from the ctrl block (CTRL_SIZE fp64 slots on the device).
+# ---------------------------------------------------------------------
+def tcg_update(eta: Tensor, rvec: Tensor, delta: Tensor, Hd: Tensor,
+               eta_snap: Tensor, delta_snap: Tensor, ctrl: Tensor) -> None:
+    """Snapshot row j = C_ITER, eta += coef * delta, and unless a stop is
+    pending r += coef * Hd with ||r||^2 added to C_DOT1. Runs only in
+    status ST_RUN."""
+    for t in (eta, rvec, delta, Hd, eta_snap, delta_snap, ctrl):
+        _chk(t)
+    total = eta.numel()
+    assert rvec.numel() == delta.numel() == Hd.numel() == total
+    assert eta_snap.numel() == delta_snap.numel()
+    assert eta_snap.numel() % total == 0 and ctrl.numel() >= CTRL_SIZE
+    _lib.dpo_tcg_update(_p(eta), _p(rvec), _p(delta), _p(Hd), _p(eta_snap),
+                        _p(delta_snap), _p(ctrl), total, _stream(eta))
+
+
+def tcg_delta(delta: Tensor, z: Tensor, ctrl: Tensor) -> None:
+    """delta = -z + C_BETA * delta in place (status ST_RUN only)."""
+    _chk(delta); _chk(z); _chk(ctrl)
+    assert z.numel() == delta.numel() and ctrl.numel() >= CTRL_SIZE
+    _lib.dpo_tcg_delta(_p(delta), _p(z), _p(ctrl), delta.numel(),
+                       _stream(delta))
+
+
+def form_step(step: Tensor, eta: Tensor, eta_snap: Tensor,
+              delta_snap: Tensor, ctrl: Tensor) -> None:
+    """step = eta when C_USE_CURRENT, else snapshot row C_JSTAR of eta
+    plus C_TAUSTAR times that row of delta (status ST_TCG_STOP only)."""
+    for t in (step, eta, eta_snap, delta_snap, ctrl):
+        _chk(t)
+    total = step.numel()
+    assert eta.numel() == total and eta_snap.numel() == delta_snap.numel()
+    assert eta_snap.numel() % total == 0 and ctrl.numel() >= CTRL_SIZE
+    _lib.dpo_form_step(_p(step), _p(eta), _p(eta_snap), _p(delta_snap),
+                       _p(ctrl), total, _stream(step))
+
+
+def axpby(A: Tensor, B: Optional[Tensor], a: float, b: float,
+          out: Optional[Tensor] = None) -> Tensor:
+    """out = a * A + b * B (B optional)."""
+    _chk(A)
+    if B is not None:
+        _chk(B)
+        assert B.numel() == A.numel()
+    if out is None:
+        out = torch.empty_like(A)
+    _chk(out)
+    assert out.numel() == A.numel()
+    _lib.dpo_axpby(_p(A), _p(B), a, b, _p(out), A.numel(), _stream(A))
+    return out
+
+
+def dots(A: Tensor, B: Tensor, C: Optional[Tensor], ctrl: Tensor,
+         slot: int, slot2: int = -1, guard: int = GUARD_NONE) -> None:
+    """ctrl[slot] += <A, B>; with C and slot2 >= 0 also ctrl[slot2] +=
+    <A, C>."""
+    _chk(A); _chk(B); _chk(ctrl)
+    assert B.numel() == A.numel() and ctrl.numel() >= CTRL_SIZE
+    assert 0 <= slot < CTRL_SIZE and -1 <= slot2 < CTRL_SIZE
+    if C is not None:
+        _chk(C)
+        assert C.numel() == A.numel()
+    _lib.dpo_dots(_p(A), _p(B), _p(C), _p(ctrl), slot, slot2, A.numel(),
+                  guard, _stream(A))
+
+
+# ---------------------------------------------------------------------
 # Device-resident RBCD local solve
 # ---------------------------------------------------------------------
 class DeviceSolver:
@@ -270,6 +376,7 @@ class DeviceSolver:
 
     def __init__(self, n: int, d: int, r: int, device, max_inner: int = 10):
         assert max_inner <= MAX_TCG
+        _check_shape(d, r)
         self.n, self.d, self.r = n, d, r
         self.dh = d + 1
         self.N = self.dh * n
@@ -453,6 +560,7 @@ class DeviceGroup:
 def gnc_weights(X: Tensor, nbr: Tensor, g: dict, weights: Tensor,
                 d: int, r: int, mu: float, barc_sq: float) -> None:
     """Launch the GNC-TLS weight-update kernel over g['ne'] edges."""
+    _check_shape(d, r)
     _lib.dpo_gnc_weights(
         _p(X), _p(nbr), _p(g["e1_idx"]), _p(g["e1_nbr"]), _p(g["e2_idx"]),
         _p(g["e2_nbr"]), _p(g["R"]), _p(g["t"]), _p(g["kappa"]),

@@ -1,0 +1,746 @@
+"""References, input builders and tolerance helpers of the kernel test
+matrix (tests/test_kernel_matrix.py). Plain fp64 NumPy / torch on the
+CPU, importable without a GPU; tests/test_kernel_refs.py checks the
+helpers themselves.
+
+Tolerance rule (docs/DESIGN.md, "Kernel test matrix"):
+  * anything that is a sum of K products sum_i a_i b_i is compared under
+    the classical bound |gpu - ref| <= 2 K eps sum_i |a_i||b_i|, which
+    holds for every summation order and with or without FMA contraction
+    (each side is within K (eps / 2) sum|a||b| of the exact value, the
+    factor 2 is head room). sop_bound() computes it from abs() copies of
+    the operands.
+  * the tangent projection propagates that bound through its two small
+    products (tangent_project_bound()).
+  * the block-Jacobi solve uses the forward error bound of a backward
+    stable solve, cond(block) 64 eps ||v|| (jacobi_tol()).
+  * the polar projection uses the error model of the Newton-Schulz
+    iteration on the Gram matrix, 8 eps cond(M)^2 + 16 eps (polar_tol()).
+None of these is fitted to what the kernels return.
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional
+
+import numpy as np
+import torch
+
+from dpo_amd.ops import cpu_ref
+from dpo_amd.quadratic import BSRMatrix
+
+Tensor = torch.Tensor
+
+EPS = float(np.finfo(np.float64).eps)
+
+# the (d, r) pairs the HIP extension compiles, read from the one table
+SHAPES = [(d, r) for d in sorted(cpu_ref.CERT_SHAPES)
+          for r in cpu_ref.CERT_SHAPES[d]]
+RS = sorted({r for _, r in SHAPES})
+
+# thread-per-pose kernels: one thread, a partly filled block, one full
+# 256-thread block, and one thread in a second block
+N_POSE = (1, 65, 256, 257)
+
+
+def poses_per_block(d: int, r: int) -> int:
+    """Poses per 256-thread block of the tile-per-pose kernels."""
+    return 256 // ((d + 1) * r)
+
+
+def n_tile(d: int, r: int):
+    """Pose counts for tile-per-pose kernels: one pose, one full block,
+    one pose in a second block, a fourth block with one pose, 257."""
+    pb = poses_per_block(d, r)
+    return tuple(sorted({1, pb, pb + 1, 3 * pb + 1, 257}))
+
+
+def gen(*key) -> torch.Generator:
+    """Fixed per-case generator."""
+    seed = 1469598103
+    for k in key:
+        seed = (seed * 1000003 + int(k)) % (2 ** 31 - 1)
+    return torch.Generator().manual_seed(seed)
+
+
+def randn(g, *shape) -> Tensor:
+    return torch.randn(*shape, dtype=torch.float64, generator=g)
+
+
+# ---------------------------------------------------------------------
+# sum-of-products bound
+# ---------------------------------------------------------------------
+def sop_bound(abs_sum, K: int):
+    """2 K eps S for S = sum |a_i||b_i| (tensor or float), K terms."""
+    return 2.0 * K * EPS * abs_sum
+
+
+def matmul_bound(A: Tensor, B: Tensor, K: int) -> Tensor:
+    """Entry-wise bound for A @ B with at most K accumulated terms."""
+    return sop_bound(A.abs() @ B.abs(), K)
+
+
+def dot_bound(a: Tensor, b: Tensor) -> float:
+    return float(sop_bound((a.abs() * b.abs()).sum(), a.numel()))
+
+
+def tangent_project_bound(X: Tensor, A: Tensor, d: int,
+                          bA: Optional[Tensor] = None) -> Tensor:
+    """Entry-wise bound for P = A - sym(Y A^T) Y at X (Y = Stiefel rows),
+    given an entry-wise bound bA on the error already in A. Propagates
+    the sum-of-products bound through S = sym(Y A^T) (r terms) and S Y
+    (d terms); the final subtraction adds one rounding of the result."""
+    N, r = A.shape
+    dh = d + 1
+    if bA is None:
+        bA = torch.zeros_like(A)
+    Yb = X.view(-1, dh, r)[:, :d, :].abs()
+    Ab = A.view(-1, dh, r)[:, :d, :].abs()
+    bAb = bA.view(-1, dh, r)[:, :d, :]
+    # |delta S| <= sym(|Y| bA^T) + 2 r eps sym(|Y||A|^T)
+    YA = torch.bmm(Yb, Ab.transpose(1, 2))
+    Sabs = 0.5 * (YA + YA.transpose(1, 2))
+    YbA = torch.bmm(Yb, bAb.transpose(1, 2))
+    dS = 0.5 * (YbA + YbA.transpose(1, 2)) + sop_bound(Sabs, r + 1)
+    SY = torch.bmm(Sabs, Yb)
+    out = bA.clone().view(-1, dh, r)
+    out[:, :d, :] += torch.bmm(dS, Yb) + sop_bound(SY, d + 1) \
+        + EPS * (Ab + SY)
+    return out.view(N, r)
+
+
+# ---------------------------------------------------------------------
+# block-sparse test matrices
+# ---------------------------------------------------------------------
+def random_bsr(n: int, dh: int, g: torch.Generator, hub_degree: int = 40):
+    """Symmetric BSRMatrix with random fp64 blocks (B_ji = B_ij^T; not
+    PSD): every diagonal block, a chain, about n random extra pairs and
+    one hub pose with about hub_degree neighbours, so that row lengths
+    vary from 2 to more than 40."""
+    pairs = {(i, i) for i in range(n)}
+    pairs |= {(i, i + 1) for i in range(n - 1)}
+    if n > 2:
+        ij = torch.randint(0, n, (n, 2), generator=g).tolist()
+        pairs |= {(min(i, j), max(i, j)) for i, j in ij if i != j}
+        hub = n // 3
+        nb = torch.randperm(n, generator=g)[:min(hub_degree, n - 1) + 1]
+        pairs |= {(min(hub, j), max(hub, j)) for j in nb.tolist() if j != hub}
+    upper = sorted(pairs)
+    blocks = randn(g, len(upper), dh, dh)
+    rows = {}
+    for (i, j), B in zip(upper, blocks):
+        if i == j:
+            rows.setdefault(i, {})[i] = 0.5 * (B + B.T)
+        else:
+            rows.setdefault(i, {})[j] = B
+            rows.setdefault(j, {})[i] = B.T
+    row_ptr = [0]
+    col_idx = []
+    vals = []
+    for i in range(n):
+        for j in sorted(rows[i]):
+            col_idx.append(j)
+            vals.append(rows[i][j])
+        row_ptr.append(len(col_idx))
+    return BSRMatrix(n, dh,
+                     torch.tensor(row_ptr, dtype=torch.int32),
+                     torch.tensor(col_idx, dtype=torch.int32),
+                     torch.stack(vals).contiguous())
+
+
+def bsr_max_row_terms(Q: BSRMatrix) -> int:
+    """Most products accumulated into one output entry of Q @ V."""
+    rp = Q.row_ptr.cpu().numpy()
+    return int(np.diff(rp).max()) * Q.dh
+
+
+def manifold_point(n: int, d: int, r: int, g: torch.Generator) -> Tensor:
+    return cpu_ref.stiefel_project(randn(g, (d + 1) * n, r), d)
+
+
+# ---------------------------------------------------------------------
+# polar projection: error model, emulation, inputs
+# ---------------------------------------------------------------------
+POLAR_CONDS = (1.0, 1e2, 1e4)
+POLAR_SCALES = (1e-3, 1.0, 1e3)
+RETRACT_ETA_NORMS = (1e-8, 1e-2, 1.0, 1e2)
+
+
+def polar_tol(cond):
+    """Error model of the GPU polar projection: it forms the Gram matrix
+    M M^T, whose condition number is cond(M)^2, and iterates on it in
+    fp64, so the factor is accurate to a multiple of eps cond(M)^2."""
+    return 8.0 * EPS * np.asarray(cond, dtype=np.float64) ** 2 + 16.0 * EPS
+
+
+def block_conds(M: Tensor, d: int) -> np.ndarray:
+    """cond of the d x r Stiefel block of every pose."""
+    s = torch.linalg.svdvals(M.view(-1, d + 1, M.shape[1])[:, :d, :])
+    return (s[:, 0] / s[:, -1]).numpy()
+
+
+def polar_emulation(M: Tensor, d: int) -> Tensor:
+    """NumPy emulation of the algorithm the GPU polar projection uses:
+    coupled Newton-Schulz iteration for Gram^{-1/2} on the trace-scaled
+    d x d Gram matrix, at most 40 iterations, stopped when the update
+    factor is the identity to 1e-15; result Gram^{-1/2} M. A vanishing
+    Gram trace gives a zero block. Translation rows pass through."""
+    r = M.shape[1]
+    Mb = M.view(-1, d + 1, r).numpy().copy()
+    Y = Mb[:, :d, :]
+    S = Y @ Y.transpose(0, 2, 1)
+    tr = np.trace(S, axis1=1, axis2=2)
+    ok = tr > 1e-300
+    I = np.broadcast_to(np.eye(d), S.shape)
+    with np.errstate(all="ignore"):
+        Yk = S / np.where(ok, tr, 1.0)[:, None, None]
+        Zk = I.copy()
+        active = ok.copy()
+        for _ in range(40):
+            if not active.any():
+                break
+            T = 0.5 * (3.0 * I - Zk @ Yk)
+            Yn, Zn = Yk @ T, T @ Zk
+            Yk = np.where(active[:, None, None], Yn, Yk)
+            Zk = np.where(active[:, None, None], Zn, Zk)
+            active &= ~(((T - I) ** 2).sum(axis=(1, 2)) < 1e-30)
+        out = (Zk / np.sqrt(np.where(ok, tr, 1.0))[:, None, None]) @ Y
+    out[~ok] = 0.0
+    Mb[:, :d, :] = out
+    return torch.from_numpy(Mb).view_as(M)
+
+
+def polar_errors(out: Tensor, M: Tensor, d: int):
+    """Per pose: max |out - SVD polar| and ||Y Y^T - I||_inf on the
+    Stiefel rows; max relative deviation of the translation rows."""
+    r = M.shape[1]
+    ref = cpu_ref.stiefel_project(M, d).view(-1, d + 1, r)
+    ob = out.view(-1, d + 1, r)
+    err = (ob[:, :d] - ref[:, :d]).abs().amax(dim=(1, 2)).numpy()
+    G = torch.bmm(ob[:, :d], ob[:, :d].transpose(1, 2)) - torch.eye(
+        d, dtype=torch.float64)
+    orth = G.abs().sum(dim=2).amax(dim=1).numpy()
+    return err, orth
+
+
+def cond_blocks(n: int, d: int, r: int, cond: float, scale: float,
+                g: torch.Generator) -> Tensor:
+    """(N, r) input whose Stiefel blocks are U diag(s) V^T with singular
+    values log-spaced in [scale / cond, scale]; Gaussian translations."""
+    U = torch.linalg.qr(randn(g, n, d, d))[0]
+    V = torch.linalg.qr(randn(g, n, r, d))[0]
+    s = scale * torch.logspace(0.0, -math.log10(cond), d,
+                               dtype=torch.float64)
+    M = randn(g, n, d + 1, r)
+    M[:, :d, :] = torch.bmm(U * s[None, None, :], V.transpose(1, 2))
+    return M.reshape(n * (d + 1), r).contiguous()
+
+
+def retraction_inputs(n: int, d: int, r: int, eta_norm: float,
+                      g: torch.Generator):
+    """X on the manifold and a tangent eta with per-pose Stiefel-block
+    Frobenius norm eta_norm. Tangency makes Y eta^T skew, so the Gram
+    matrix of Y + eta is I + eta eta^T and cond(Y + eta) <=
+    sqrt(1 + eta_norm^2): the retraction stays inside the domain of the
+    Gram-matrix iteration for every step length."""
+    X = manifold_point(n, d, r, g)
+    eta = cpu_ref.tangent_project(X, randn(g, (d + 1) * n, r), d)
+    eb = eta.view(n, d + 1, r)
+    nrm = eb[:, :d, :].flatten(1).norm(dim=1)
+    eb[:, :d, :] *= (eta_norm / nrm)[:, None, None]
+    return X, eta.contiguous()
+
+
+POLAR_N = 257  # conditioning cases: two blocks of the per-pose kernel
+POLAR_ABC = (1.7, -0.7, 0.3)
+
+
+def polar_form_inputs(d: int, r: int, n: int):
+    """Operands of the three polar_affine forms at one (shape, n):
+    {form: (A, B, C, ca, cb, cc)}. 1-operand: a Gaussian matrix;
+    2-operand: the retraction X + eta; 3-operand: the Nesterov-style
+    combination 1.7 A - 0.7 B + 0.3 C of a manifold point and two
+    Gaussian matrices."""
+    g = gen(3, d, r, n)
+    N = (d + 1) * n
+    X = manifold_point(n, d, r, g)
+    eta = 0.3 * cpu_ref.tangent_project(X, randn(g, N, r), d)
+    ca, cb, cc = POLAR_ABC
+    return {
+        "one": (randn(g, N, r), None, None, 1.0, 0.0, 0.0),
+        "two": (X, eta, None, 1.0, 1.0, 0.0),
+        "three": (X, randn(g, N, r), randn(g, N, r), ca, cb, cc),
+    }
+
+
+def affine(A, B, C, ca, cb, cc) -> Tensor:
+    M = ca * A
+    if B is not None:
+        M = M + cb * B
+    if C is not None:
+        M = M + cc * C
+    return M
+
+
+def polar_cond_cases(d: int, r: int):
+    """[(label, M)]: constructed-spectrum blocks, every cond x scale."""
+    out = []
+    for ci, cond in enumerate(POLAR_CONDS):
+        for si, scale in enumerate(POLAR_SCALES):
+            g = gen(4, d, r, ci, si)
+            out.append((f"cond{cond:g}-scale{scale:g}", cond,
+                        cond_blocks(POLAR_N, d, r, cond, scale, g)))
+    return out
+
+
+def polar_retract_cases(d: int, r: int):
+    """[(label, cond bound, X, eta)] for every step length."""
+    out = []
+    for ei, en in enumerate(RETRACT_ETA_NORMS):
+        X, eta = retraction_inputs(POLAR_N, d, r, en, gen(5, d, r, ei))
+        out.append((f"eta{en:g}", math.sqrt(1.0 + en * en), X, eta))
+    return out
+
+
+# ---------------------------------------------------------------------
+# block-Jacobi
+# ---------------------------------------------------------------------
+JACOBI_CONDS = (1.0, 1e3, 1e6)
+
+
+def spd_blocks(n: int, dh: int, g: torch.Generator) -> Tensor:
+    """(n, dh, dh) SPD blocks W diag(lam) W^T with lam log-spaced in
+    [1, cond], cond cycling through JACOBI_CONDS over the poses. The
+    smallest eigenvalue is 1, so ||A^-1|| = 1 and ||x|| <= ||v||."""
+    W = torch.linalg.qr(randn(g, n, dh, dh))[0]
+    conds = torch.tensor([JACOBI_CONDS[i % len(JACOBI_CONDS)]
+                          for i in range(n)], dtype=torch.float64)
+    t = torch.linspace(0.0, 1.0, dh, dtype=torch.float64)
+    lam = conds[:, None] ** t[None, :]
+    A = torch.bmm(W * lam[:, None, :], W.transpose(1, 2))
+    return 0.5 * (A + A.transpose(1, 2))
+
+
+def jacobi_tol(blocks: Tensor, V: Tensor) -> Tensor:
+    """(N, r) tolerance cond(block) 64 eps ||v||, ||v|| the 2-norm of the
+    pose's right-hand-side column: the forward error cond eps ||x|| of a
+    backward-stable solve, with ||x|| <= ||A^-1|| ||v|| = ||v|| for the
+    blocks of spd_blocks()."""
+    n, dh, _ = blocks.shape
+    r = V.shape[1]
+    ev = torch.linalg.eigvalsh(blocks)
+    cond = ev[:, -1] / ev[:, 0]
+    vn = V.view(n, dh, r).norm(dim=1)                    # (n, r)
+    tol = 64.0 * EPS * cond[:, None] * vn
+    return tol[:, None, :].expand(n, dh, r).reshape(n * dh, r)
+
+
+# ---------------------------------------------------------------------
+# GNC-TLS weights
+# ---------------------------------------------------------------------
+def gnc_residual_sq(P1, P2, R, t, kappa, tau, d):
+    """r^2 = kappa ||R^T Y1t - Y2t||_F^2 + tau ||p2 - p1 - t^T Y1t||^2 on
+    the lifted poses P1, P2 (ne, d+1, r) (NumPy)."""
+    Y1, p1 = P1[:, :d, :], P1[:, d, :]
+    Y2, p2 = P2[:, :d, :], P2[:, d, :]
+    rot = np.einsum("eab,eak->ebk", R, Y1) - Y2
+    tran = p2 - p1 - np.einsum("ea,eak->ek", t, Y1)
+    return kappa * (rot ** 2).sum(axis=(1, 2)) + tau * (tran ** 2).sum(axis=1)
+
+
+def gnc_weight_ref(r_sq, mu: float, barc: float) -> np.ndarray:
+    """The project's own GNC-TLS weight function (robust.py), per edge."""
+    from dpo_amd.robust import RobustCost
+    from dpo_amd.types import RobustCostParams, RobustCostType
+    rc = RobustCost(RobustCostType.GNC_TLS, RobustCostParams(gnc_barc=barc))
+    rc.mu = mu
+    return np.array([rc.weight(math.sqrt(v)) for v in r_sq])
+
+
+def gnc_tol(mu: float) -> float:
+    """sqrt(barc^2 mu (mu + 1) / r^2) - mu cancels at large mu."""
+    return 64.0 * EPS * (1.0 + mu)
+
+
+# ---------------------------------------------------------------------
+# tCG control block: layout and a Python model of the control steps
+# ---------------------------------------------------------------------
+(C_STATUS, C_FX, C_GN0SQ, C_RR, C_ZR, C_EPE, C_EPD, C_DPD, C_COEF, C_BETA,
+ C_ITER, C_J, C_RADIUS, C_FPROP, C_DM, C_JSTAR, C_TAUSTAR, C_USE_CURRENT,
+ C_STOP_PENDING, C_BOUND, C_GN1SQ, C_RHO, C_HLEN, C_SHRINKS, C_DOT0, C_DOT1,
+ C_DOT2, C_DOT3) = range(28)
+C_HIST = 32
+MAX_TCG = 16
+CTRL_SIZE = C_HIST + 5 * MAX_TCG
+ST_RUN, ST_TCG_STOP, ST_ACCEPTED, ST_GIVE_UP, ST_NO_UPDATE = range(5)
+
+
+def H_ZR(j): return C_HIST + j
+def H_DHD(j): return C_HIST + MAX_TCG + j
+def H_EPE(j): return C_HIST + 2 * MAX_TCG + j
+def H_EPD(j): return C_HIST + 3 * MAX_TCG + j
+def H_DPD(j): return C_HIST + 4 * MAX_TCG + j
+
+
+def _steihaug_step(z_r, d_Hd, e_Pe, e_Pd, d_Pd, radius):
+    """One Steihaug-Toint decision (solver.truncated_cg): returns
+    (hit, coef, e_Pe_new); hit = negative curvature or boundary, coef =
+    tau to the boundary, else the CG step length alpha."""
+    with np.errstate(all="ignore"):
+        alpha = np.float64(z_r) / np.float64(d_Hd) if d_Hd != 0 else math.inf
+        e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd
+    if d_Hd <= 0 or e_Pe_new >= radius * radius:
+        disc = e_Pd * e_Pd + d_Pd * (radius * radius - e_Pe)
+        tau = ((-e_Pd + math.sqrt(max(disc, 0.0))) / d_Pd
+               if d_Pd > 0 else 0.0)
+        return True, tau, e_Pe_new
+    return False, float(alpha), float(e_Pe_new)
+
+
+class CtrlModel:
+    """Python model of the scalar tCG / trust-region control steps on a
+    CTRL_SIZE fp64 block. Each method is one control kernel: it consumes
+    the dot products the vector kernels left in the C_DOT* slots and
+    clears them, as the device contract requires."""
+
+    def __init__(self, ctrl=None):
+        self.c = (np.zeros(CTRL_SIZE) if ctrl is None
+                  else np.array(ctrl, dtype=np.float64))
+        assert self.c.shape == (CTRL_SIZE,)
+
+    def init(self, tol, Delta0, theta, kappa):
+        c = self.c
+        # C_DOT0 = <QX + G, X>, C_DOT2 = <G, X>, C_DOT1 = ||grad||^2
+        c[C_FX] = 0.5 * (c[C_DOT0] + c[C_DOT2])
+        gn0sq = c[C_DOT1]
+        c[C_GN0SQ] = gn0sq
+        c[C_RR] = gn0sq
+        nr0 = math.sqrt(gn0sq)
+        c[C_BOUND] = nr0 * min(nr0 ** theta, kappa)
+        c[C_RADIUS] = Delta0
+        for s in (C_EPE, C_EPD, C_ITER, C_J, C_USE_CURRENT, C_STOP_PENDING,
+                  C_BETA, C_DOT0, C_DOT1, C_DOT2, C_DOT3):
+            c[s] = 0.0
+        c[C_STATUS] = ST_NO_UPDATE if nr0 < tol else ST_RUN
+
+    def z0(self):
+        c = self.c
+        if c[C_STATUS] != ST_RUN:
+            return
+        c[C_ZR] = c[C_DOT0]
+        c[C_DPD] = c[C_DOT0]
+        c[C_DOT0] = 0.0
+
+    def alpha(self):
+        c = self.c
+        if c[C_STATUS] != ST_RUN:
+            return
+        j = int(c[C_ITER])
+        d_Hd = c[C_DOT0]
+        c[C_DOT0] = 0.0
+        c[H_ZR(j)], c[H_DHD(j)] = c[C_ZR], d_Hd
+        c[H_EPE(j)], c[H_EPD(j)], c[H_DPD(j)] = c[C_EPE], c[C_EPD], c[C_DPD]
+        hit, coef, e_Pe_new = _steihaug_step(
+            c[C_ZR], d_Hd, c[C_EPE], c[C_EPD], c[C_DPD], c[C_RADIUS])
+        c[C_COEF] = coef
+        c[C_STOP_PENDING] = 1.0 if hit else 0.0
+        if not hit:
+            c[C_EPE] = e_Pe_new
+
+    def rr(self):
+        c = self.c
+        if c[C_STATUS] != ST_RUN:
+            return
+        j = int(c[C_ITER])
+        if c[C_STOP_PENDING] != 0.0:
+            c[C_STATUS] = ST_TCG_STOP
+            c[C_J] = j
+            c[C_HLEN] = j + 1
+            c[C_USE_CURRENT] = 0.0
+            return
+        rr = c[C_DOT1]
+        c[C_DOT1] = 0.0
+        c[C_RR] = rr
+        if math.sqrt(rr) <= c[C_BOUND]:
+            c[C_STATUS] = ST_TCG_STOP
+            c[C_J] = j + 1
+            c[C_HLEN] = j + 1
+            c[C_USE_CURRENT] = 1.0
+
+    def beta(self):
+        c = self.c
+        if c[C_STATUS] != ST_RUN:
+            return
+        z_r_new = c[C_DOT0]
+        c[C_DOT0] = 0.0
+        with np.errstate(all="ignore"):
+            beta = z_r_new / c[C_ZR]
+        c[C_BETA] = beta
+        c[C_EPD] = beta * (c[C_EPD] + c[C_COEF] * c[C_DPD])
+        c[C_DPD] = z_r_new + beta * beta * c[C_DPD]
+        c[C_ZR] = z_r_new
+        c[C_ITER] += 1.0
+
+    def tcg_end(self):
+        c = self.c
+        if c[C_STATUS] != ST_RUN:
+            return
+        c[C_STATUS] = ST_TCG_STOP
+        c[C_J] = c[C_ITER]
+        c[C_HLEN] = c[C_ITER]
+        c[C_USE_CURRENT] = 1.0
+
+    def candidate(self):
+        """Replay the stored Krylov scalars at the current radius."""
+        c = self.c
+        if c[C_STATUS] != ST_TCG_STOP:
+            return
+        dm = 0.0
+        jstar = -1
+        for j in range(min(int(c[C_HLEN]), MAX_TCG)):
+            z_r, d_Hd = c[H_ZR(j)], c[H_DHD(j)]
+            hit, coef, _ = _steihaug_step(z_r, d_Hd, c[H_EPE(j)],
+                                          c[H_EPD(j)], c[H_DPD(j)],
+                                          c[C_RADIUS])
+            if hit:
+                dm += coef * z_r - 0.5 * coef * coef * d_Hd
+                jstar = j
+                c[C_JSTAR] = j
+                c[C_TAUSTAR] = coef
+                break
+            dm += 0.5 * coef * z_r
+        c[C_USE_CURRENT] = 1.0 if jstar < 0 else 0.0
+        c[C_DM] = dm
+        c[C_DOT0] = 0.0
+        c[C_DOT2] = 0.0
+
+    def accept(self, accept_rho):
+        c = self.c
+        if c[C_STATUS] != ST_TCG_STOP:
+            return
+        # C_DOT0 = <Q Xp, Xp>, C_DOT2 = <G, Xp>
+        fprop = 0.5 * c[C_DOT0] + c[C_DOT2]
+        c[C_DOT0] = 0.0
+        c[C_DOT2] = 0.0
+        c[C_FPROP] = fprop
+        rho = (c[C_FX] - fprop) / max(c[C_DM], 1e-300)
+        c[C_RHO] = rho
+        if rho > accept_rho and fprop <= c[C_FX]:
+            c[C_STATUS] = ST_ACCEPTED
+
+    def shrink(self):
+        c = self.c
+        if c[C_STATUS] != ST_TCG_STOP:
+            return
+        c[C_RADIUS] *= 0.25
+        c[C_SHRINKS] += 1.0
+
+
+def model_decrease_from_history(c) -> float:
+    """-<g, s> - 0.5 <s, H s> of the step the stored history describes
+    at radius c[C_RADIUS], from the CG identities: a full step j lowers
+    the model by 0.5 alpha_j <z_j, r_j>, a step tau along delta_j by
+    tau <z_j, r_j> - 0.5 tau^2 <delta_j, H delta_j>. tau is re-derived
+    as the positive root of ||eta_j + tau delta_j||_P = radius."""
+    R2 = c[C_RADIUS] ** 2
+    dm = 0.0
+    for j in range(min(int(c[C_HLEN]), MAX_TCG)):
+        z_r, d_Hd = c[H_ZR(j)], c[H_DHD(j)]
+        e_Pe, e_Pd, d_Pd = c[H_EPE(j)], c[H_EPD(j)], c[H_DPD(j)]
+        full = None
+        if d_Hd > 0:
+            a = z_r / d_Hd
+            if e_Pe + 2 * a * e_Pd + a * a * d_Pd < R2:
+                full = a
+        if full is None:
+            if d_Pd > 0:
+                roots = np.roots([d_Pd, 2 * e_Pd, e_Pe - R2])
+                tau = float(max(roots.real)) if R2 >= e_Pe else 0.0
+            else:
+                tau = 0.0
+            return dm + tau * z_r - 0.5 * tau * tau * d_Hd
+        dm += 0.5 * full * z_r
+    return dm
+
+
+def ctrl_tol(model: np.ndarray) -> np.ndarray:
+    """Per-slot tolerance for comparing a device control block with the
+    model: the steps are a handful of fp64 operations that the compiler
+    may contract into FMAs, so 64 eps relative to the slot's magnitude
+    (floor 1) — not bit equality. Flags, counters and untouched slots
+    are integers or copies and compare equal under it as well."""
+    return 64.0 * EPS * np.maximum(1.0, np.abs(model))
+
+
+def model_solve(problem, X0: Tensor, tol: float, Delta0: float,
+                max_inner: int, accept_rho: float = 0.1,
+                max_shrink: int = 10, theta: float = 1.0,
+                kappa: float = 0.1):
+    """One RBCD local solve with the vector work in torch on the CPU and
+    every scalar decision taken by CtrlModel, in the order the device
+    solve enqueues them. Returns (X, ctrl block, final status)."""
+    assert max_inner <= MAX_TCG
+    man = problem.manifold
+    m = CtrlModel()
+    c = m.c
+    G = problem._g()
+    A = problem.Q.spmm(X0) + G
+    grad = man.project_tangent(X0, A)
+    c[C_DOT1] = float((grad * grad).sum())
+    c[C_DOT0] = float((A * X0).sum())
+    c[C_DOT2] = float((G * X0).sum())
+    m.init(tol, Delta0, theta, kappa)
+    if c[C_STATUS] != ST_RUN:
+        return X0, c, int(c[C_STATUS])
+    r = grad.clone()
+    z = problem.precondition(X0, r)
+    c[C_DOT0] = float((z * r).sum())
+    m.z0()
+    delta = -z
+    eta = torch.zeros_like(grad)
+    eta_snap, delta_snap = [], []
+    for _ in range(max_inner):
+        if c[C_STATUS] != ST_RUN:
+            break
+        Hd = man.project_tangent(X0, problem.hess_vec(delta))
+        c[C_DOT0] = float((delta * Hd).sum())
+        m.alpha()
+        eta_snap.append(eta.clone())
+        delta_snap.append(delta.clone())
+        eta = eta + c[C_COEF] * delta
+        if c[C_STOP_PENDING] == 0.0:
+            r = r + c[C_COEF] * Hd
+            c[C_DOT1] = float((r * r).sum())
+        m.rr()
+        if c[C_STATUS] != ST_RUN:
+            break
+        z = problem.precondition(X0, r)
+        c[C_DOT0] = float((z * r).sum())
+        m.beta()
+        delta = -z + c[C_BETA] * delta
+    m.tcg_end()
+    for attempt in range(max_shrink + 1):
+        if attempt:
+            m.shrink()
+        m.candidate()
+        if c[C_USE_CURRENT] != 0.0:
+            step = eta
+        else:
+            j = int(c[C_JSTAR])
+            step = eta_snap[j] + c[C_TAUSTAR] * delta_snap[j]
+        Xp = man.retract(X0, step)
+        c[C_DOT0] = float((problem.Q.spmm(Xp) * Xp).sum())
+        c[C_DOT2] = float((G * Xp).sum())
+        m.accept(accept_rho)
+        if c[C_STATUS] == ST_ACCEPTED:
+            return Xp, c, ST_ACCEPTED
+    return X0, c, ST_GIVE_UP
+
+
+def host_solve(problem, X0: Tensor, tol: float, Delta0: float,
+               max_inner: int):
+    """The host QuadraticOptimizer's RBCD solve, instrumented: returns
+    (X, OptResult, tCG runs, Hessian products of the last run). The last
+    count is the tCG iteration count, the device's history length."""
+    from dpo_amd.solver import QuadraticOptimizer, TRParams
+    from dpo_amd.types import OptAlgorithm
+    runs = []
+    hess_vec, precondition = problem.hess_vec, problem.precondition
+    state = {"fresh": True}
+
+    def counted_hess_vec(V):
+        if state["fresh"]:
+            runs.append(0)
+            state["fresh"] = False
+        runs[-1] += 1
+        return hess_vec(V)
+
+    def retract(X, eta, _orig=problem.manifold.retract):
+        state["fresh"] = True
+        return _orig(X, eta)
+
+    problem.hess_vec = counted_hess_vec
+    problem.manifold.retract = retract
+    try:
+        tr = TRParams(tolerance=tol, initial_radius=Delta0, max_iterations=1,
+                      max_inner_iterations=max_inner)
+        opt = QuadraticOptimizer(problem, OptAlgorithm.RTR, tr)
+        X = opt.optimize(X0.clone())
+    finally:
+        del problem.hess_vec
+        del problem.manifold.retract
+    return X, opt.result, len(runs), (runs[-1] if runs else 0)
+
+
+def solve_problem(d: int, r: int, with_g: bool = False):
+    """Measurement-built PSD problem with 257 <= n <= 350 poses (two
+    blocks of every thread-per-pose kernel), Jacobi preconditioner, and
+    a manifold start point. d = 3: grid3d(side=7), n = 343; d = 2:
+    city2d(side=18), n = 324."""
+    from dpo_amd.quadratic import (QuadraticProblem,
+                                   assemble_connection_laplacian)
+    from dpo_amd.synthetic import city2d, grid3d
+    meas, n = grid3d(side=7, seed=2) if d == 3 else city2d(side=18, seed=2)
+    Q = assemble_connection_laplacian(meas, n, d)
+    g = gen(7, d, r)
+    X = manifold_point(n, d, r, g)
+    p = QuadraticProblem(n, d, r, precond="jacobi")
+    p.set_q(Q)
+    if with_g:
+        p.set_g(randn(g, (d + 1) * n, r))
+    return p, X
+
+
+def small_problem(d: int, r: int, n: int, g: torch.Generator,
+                  with_g: bool = True):
+    """PSD problem on exactly n poses: a measurement-built graph cut to
+    its first n poses (the odometry chain keeps it connected)."""
+    from dpo_amd.quadratic import (QuadraticProblem,
+                                   assemble_connection_laplacian)
+    from dpo_amd.synthetic import city2d, grid3d
+    if d == 3:
+        side = max(2, math.ceil(n ** (1.0 / 3.0) - 1e-9))
+        meas, n_all = grid3d(side=side, seed=1)
+    else:
+        side = max(2, math.ceil(math.sqrt(n) - 1e-9))
+        meas, n_all = city2d(side=side, seed=1)
+    assert n_all >= n
+    meas = [m for m in meas if m.p1 < n and m.p2 < n]
+    p = QuadraticProblem(n, d, r, precond="jacobi")
+    if meas:
+        p.set_q(assemble_connection_laplacian(meas, n, d))
+    else:
+        # a single pose has no edges: one PSD diagonal block
+        assert n == 1
+        B = randn(g, d + 1, d + 1)
+        p.set_q(BSRMatrix(1, d + 1, torch.tensor([0, 1], dtype=torch.int32),
+                          torch.tensor([0], dtype=torch.int32),
+                          (B @ B.T)[None].contiguous()))
+    if with_g:
+        p.set_g(randn(g, (d + 1) * n, r))
+    return p, manifold_point(n, d, r, g)
+
+
+def eval_terms_ref(problem, X: Tensor):
+    """[f, 0.5 <X, G>, ||rgrad||^2] in fp64 on the CPU, with a bound for
+    each from the sum-of-products rule: the spmm entries carry
+    matmul_bound, the projection propagates it, and each scalar adds the
+    bound of its own final dot product."""
+    Q, d = problem.Q, problem.d
+    G = problem._g()
+    Qd = Q.to_dense()
+    K = bsr_max_row_terms(Q) + 1
+    A = Qd @ X + G
+    bA = sop_bound(Qd.abs() @ X.abs() + G.abs(), K)
+    f = 0.5 * float(((Qd @ X) * X).sum()) + float((G * X).sum())
+    xg = 0.5 * float((X * G).sum())
+    P = cpu_ref.tangent_project(X, A, d)
+    bP = tangent_project_bound(X, A, d, bA)
+    gn2 = float((P * P).sum())
+    T = X.numel()
+    b_f = float((bA * X.abs()).sum()) + float(sop_bound(
+        (A.abs() * X.abs()).sum() + (G.abs() * X.abs()).sum(), T))
+    b_xg = float(sop_bound((G.abs() * X.abs()).sum(), T))
+    b_gn2 = float((2.0 * P.abs() * bP + bP * bP).sum()) + float(
+        sop_bound((P * P).sum(), T))
+    return (np.array([f, xg, gn2]), np.array([b_f, b_xg, b_gn2]), P, bP)

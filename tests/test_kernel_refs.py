@@ -1,0 +1,245 @@
+"""CPU checks of tests/kernel_refs.py: the references, bounds and input
+builders the GPU kernel matrix relies on must themselves be right, and
+every polar-projection input used on the GPU must lie inside the stated
+domain of the Gram-matrix iteration."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import kernel_refs as kr
+from dpo_amd.ops import cpu_ref
+
+
+def test_shape_and_n_lists():
+    assert len(kr.SHAPES) == 11
+    assert (2, 2) in kr.SHAPES and (3, 8) in kr.SHAPES
+    assert (3, 9) not in kr.SHAPES and (2, 7) not in kr.SHAPES
+    # r = 6 and r = 7 (d = 3) leave a dead thread tail in each block
+    assert kr.poses_per_block(3, 6) == 10 and kr.poses_per_block(3, 7) == 9
+    assert kr.n_tile(3, 7) == (1, 9, 10, 28, 257)
+    for d, r in kr.SHAPES:
+        assert max(kr.n_tile(d, r)) <= 600
+
+
+def test_sop_bound_holds_for_any_order_and_sees_a_dropped_term():
+    g = kr.gen(1)
+    a, b = kr.randn(g, 4000), kr.randn(g, 4000)
+    bound = kr.dot_bound(a, b)
+    exact = float(np.dot(a.numpy().astype(np.longdouble),
+                         b.numpy().astype(np.longdouble)))
+    perm = torch.randperm(4000, generator=g)
+    for s in (float((a * b).sum()), float((a[perm] * b[perm]).sum()),
+              float(sum((a * b).tolist()))):
+        assert abs(s - exact) <= bound
+    assert bound < 1e-8
+    drop = float((a[1:] * b[1:]).sum())
+    assert abs(drop - exact) > 1e3 * bound
+
+
+@pytest.mark.parametrize("n", [1, 2, 65, 257])
+def test_random_bsr_is_symmetric_with_uneven_rows(n):
+    Q = kr.random_bsr(n, 4, kr.gen(2, n))
+    D = Q.to_dense()
+    assert D.shape == (4 * n, 4 * n)
+    assert torch.equal(D, D.T)
+    lens = np.diff(Q.row_ptr.numpy())
+    assert lens.min() >= 1
+    if n >= 65:
+        assert lens.max() >= 40 and lens.min() <= 4
+    ci = Q.col_idx.numpy()
+    assert ci.min() >= 0 and ci.max() < n
+
+
+def test_tangent_project_bound_covers_reordered_evaluation():
+    d, r, n = 3, 5, 65
+    g = kr.gen(3)
+    X = kr.manifold_point(n, d, r, g)
+    A = kr.randn(g, 4 * n, r)
+    ref = cpu_ref.tangent_project(X, A, d)
+    Xl = X.numpy().astype(np.longdouble).reshape(n, 4, r)
+    Al = A.numpy().astype(np.longdouble).reshape(n, 4, r)
+    Y = Xl[:, :3]
+    S = np.einsum("nak,nbk->nab", Y, Al[:, :3])
+    S = 0.5 * (S + S.transpose(0, 2, 1))
+    P = Al.copy()
+    P[:, :3] -= np.einsum("nab,nbk->nak", S, Y)
+    err = np.abs(ref.numpy().reshape(n, 4, r) - P).astype(np.float64)
+    b = kr.tangent_project_bound(X, A, d).numpy().reshape(n, 4, r)
+    assert (err <= b).all()
+    assert b.max() < 1e-13
+    assert (b[:, 3] == 0).all()      # translation rows are copies
+
+
+# ---------------------------------------------------------------- polar
+def _emulation_margin(M, d):
+    out = kr.polar_emulation(M, d)
+    err, orth = kr.polar_errors(out, M, d)
+    tol = kr.polar_tol(kr.block_conds(M, d))
+    return np.maximum(err, orth) / tol
+
+
+@pytest.mark.parametrize("d,r", kr.SHAPES)
+def test_polar_inputs_are_inside_the_domain(d, r):
+    """Under the CPU emulation of the Gram-matrix iteration, every input
+    the GPU polar tests use stays under 8 eps cond^2 + 16 eps."""
+    for n in kr.N_POSE:
+        for form, (A, B, C, ca, cb, cc) in kr.polar_form_inputs(
+                d, r, n).items():
+            M = kr.affine(A, B, C, ca, cb, cc)
+            assert kr.block_conds(M, d).max() < 1e6, (form, n)
+            assert _emulation_margin(M, d).max() <= 1.0, (form, n)
+    for label, cond, M in kr.polar_cond_cases(d, r):
+        c = kr.block_conds(M, d)
+        assert np.allclose(c, cond, rtol=1e-6), label
+        assert _emulation_margin(M, d).max() <= 1.0, label
+    for label, cbound, X, eta in kr.polar_retract_cases(d, r):
+        M = X + eta
+        assert kr.block_conds(M, d).max() <= cbound * (1 + 1e-9), label
+        assert _emulation_margin(M, d).max() <= 1.0, label
+
+
+@pytest.mark.parametrize("d,r", [(2, 2), (3, 3), (3, 5), (3, 8)])
+def test_polar_bound_is_not_vacuous(d, r):
+    """At cond(M) = 1e7 the iteration is outside its domain: the
+    emulation is off the SVD polar by about 0.15 and its Y Y^T - I
+    exceeds the bound on every block, so the GPU assertions (closeness
+    and orthonormality under one bound) would fail there."""
+    M = kr.cond_blocks(200, d, r, 1e7, 1.0, kr.gen(6, d, r))
+    out = kr.polar_emulation(M, d)
+    err, orth = kr.polar_errors(out, M, d)
+    tol = kr.polar_tol(1e7)
+    assert orth.min() > tol      # every block fails the orthonormality check
+    assert err.max() > 0.05
+
+
+def test_polar_emulation_zero_block_when_gram_trace_underflows():
+    M = torch.full((4, 5), 1e-160, dtype=torch.float64)
+    out = kr.polar_emulation(M, 3)
+    assert torch.equal(out[:3], torch.zeros(3, 5, dtype=torch.float64))
+    assert torch.equal(out[3], M[3])
+
+
+# --------------------------------------------------------------- jacobi
+@pytest.mark.parametrize("dh", [3, 4])
+def test_jacobi_blocks_and_tolerance(dh):
+    n, r = 65, 5
+    g = kr.gen(8, dh)
+    A = kr.spd_blocks(n, dh, g)
+    ev = torch.linalg.eigvalsh(A)
+    assert float(ev.min()) > 0.999
+    conds = (ev[:, -1] / ev[:, 0]).numpy()
+    assert conds.max() > 0.9e6 and conds.min() < 1.1
+    V = kr.randn(g, n * dh, r)
+    L = torch.linalg.cholesky(A)
+    ref = torch.cholesky_solve(V.view(n, dh, r), L).reshape(-1, r)
+    Al = A.numpy().astype(np.longdouble)
+    xl = np.stack([np.linalg.solve(A[i].numpy(), V.view(n, dh, r)[i].numpy())
+                   for i in range(n)])
+    # one step of refinement in extended precision
+    res = V.view(n, dh, r).numpy().astype(np.longdouble) - Al @ xl
+    xl = xl + np.stack([np.linalg.solve(A[i].numpy(),
+                                        res[i].astype(np.float64))
+                        for i in range(n)])
+    err = np.abs(ref.numpy().reshape(n, dh, r) - xl).astype(np.float64)
+    tol = kr.jacobi_tol(A, V).numpy().reshape(n, dh, r)
+    assert (err <= tol).all()
+    # a swapped pair of factor entries is far outside it
+    assert tol.max() < 1e-6 * float(V.abs().max())
+
+
+# ------------------------------------------------------------------ gnc
+def test_gnc_reference_regimes():
+    barc = 10.0
+    for mu in (1e-2, 1.0, 1e4):
+        lower = mu / (mu + 1) * barc ** 2
+        upper = (mu + 1) / mu * barc ** 2
+        w = kr.gnc_weight_ref(
+            np.array([0.5 * lower, math.sqrt(lower * upper), 2 * upper]),
+            mu, barc)
+        assert w[0] == 1.0 and w[2] == 0.0
+        # at the geometric mean r^2 = barc^2 exactly: w = sqrt(mu(mu+1)) - mu
+        assert abs(w[1] - (math.sqrt(mu * (mu + 1)) - mu)) <= kr.gnc_tol(mu)
+        assert 0.0 < w[1] < 1.0
+
+
+def test_gnc_residual_zero_for_consistent_edge():
+    d, r = 3, 5
+    g = kr.gen(9)
+    P1 = kr.manifold_point(1, d, r, g).view(1, d + 1, r).numpy()
+    R = torch.linalg.qr(kr.randn(g, d, d))[0].numpy()[None]
+    t = kr.randn(g, 1, d).numpy()
+    P2 = np.zeros_like(P1)
+    P2[:, :d] = np.einsum("eab,eak->ebk", R, P1[:, :d])
+    P2[:, d] = P1[:, d] + np.einsum("ea,eak->ek", t, P1[:, :d])
+    rsq = kr.gnc_residual_sq(P1, P2, R, t, np.array([3.0]),
+                             np.array([2.0]), d)
+    assert rsq[0] < 1e-28
+    P2[:, d, 0] += 2.0
+    rsq = kr.gnc_residual_sq(P1, P2, R, t, np.array([3.0]),
+                             np.array([2.0]), d)
+    assert abs(rsq[0] - 8.0) < 1e-12
+
+
+# ---------------------------------------------------- tCG control model
+@pytest.fixture(scope="module")
+def tcg_problem():
+    from dpo_amd.quadratic import (QuadraticProblem,
+                                   assemble_connection_laplacian)
+    from dpo_amd.synthetic import grid3d
+    meas, n = grid3d(side=4, seed=0)
+    d, r = 3, 5
+    p = QuadraticProblem(n, d, r, precond="jacobi")
+    p.set_q(assemble_connection_laplacian(meas, n, d))
+    return p, kr.manifold_point(n, d, r, kr.gen(10))
+
+
+@pytest.mark.parametrize("Delta0,status,use_current", [
+    (1e4, "converged", 1.0), (1.0, "exceeded_tr", 0.0),
+    (100.0, "exceeded_tr", 0.0)])
+def test_ctrl_model_reproduces_host_tcg(tcg_problem, Delta0, status,
+                                        use_current):
+    """The control model, driven through a whole solve, takes the host
+    optimizer's step and ends in its status."""
+    p, X0 = tcg_problem
+    Xh, res, runs, iters = kr.host_solve(p, X0, 1e-2, Delta0, 10)
+    Xm, c, st = kr.model_solve(p, X0, 1e-2, Delta0, 10)
+    assert res.tcg_status == status and runs == 1
+    assert st == kr.ST_ACCEPTED and c[kr.C_SHRINKS] == 0
+    assert c[kr.C_USE_CURRENT] == use_current
+    assert int(c[kr.C_HLEN]) == iters
+    assert torch.allclose(Xm, Xh, atol=1e-9, rtol=0)
+    assert abs(c[kr.C_FPROP] - res.f_opt) <= 1e-9 * abs(res.f_opt)
+    # model decrease recomputed from the stored history
+    dm = kr.model_decrease_from_history(c)
+    assert abs(dm - c[kr.C_DM]) <= 1e-12 * abs(dm)
+
+
+def test_ctrl_model_max_inner_cap(tcg_problem):
+    p, X0 = tcg_problem
+    Xh, res, runs, iters = kr.host_solve(p, X0, 1e-2, 1e4, 2)
+    Xm, c, st = kr.model_solve(p, X0, 1e-2, 1e4, 2)
+    assert res.tcg_status == "max_inner" and iters == 2
+    assert int(c[kr.C_HLEN]) == 2 and c[kr.C_USE_CURRENT] == 1.0
+    assert torch.allclose(Xm, Xh, atol=1e-9, rtol=0)
+
+
+def test_ctrl_model_no_update_below_tolerance(tcg_problem):
+    p, X0 = tcg_problem
+    Xm, c, st = kr.model_solve(p, X0, 1e9, 100.0, 10)
+    assert st == kr.ST_NO_UPDATE and Xm is X0
+
+
+def test_boundary_tau_lands_on_the_radius():
+    m = kr.CtrlModel()
+    c = m.c
+    c[kr.C_STATUS] = kr.ST_RUN
+    c[kr.C_ZR], c[kr.C_EPE], c[kr.C_EPD], c[kr.C_DPD] = 2.0, 1.5, 0.3, 0.8
+    c[kr.C_RADIUS] = 2.0
+    c[kr.C_DOT0] = 0.1          # alpha = 20: far past the boundary
+    m.alpha()
+    assert c[kr.C_STOP_PENDING] == 1.0
+    tau = c[kr.C_COEF]
+    lhs = 1.5 + 2 * tau * 0.3 + tau * tau * 0.8
+    assert abs(lhs - 4.0) <= 1e-12 * 4.0 and tau > 0
