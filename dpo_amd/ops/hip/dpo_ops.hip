@@ -32,6 +32,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+
 // teardown/cleanup calls whose errors are deliberately ignored
 static inline void dpo_ignore(hipError_t) {}
 
@@ -142,7 +144,7 @@ __device__ __forceinline__ bool fanin_last_block(double* ctrl) {
 // L2-visibly (the next kernel's dispatch acquire makes them visible to
 // all CUs).
 enum CtrlFuse { CF_NONE = 0, CF_Z0 = 1, CF_ALPHA = 2, CF_RR = 3,
-                CF_BETA = 4, CF_COMBINE = 5 };
+                CF_BETA = 4 };
 
 // after z0 projection+dot (C_DOT0 = <z0, r0>)
 __device__ void ctrl_tail_z0(double* ctrl) {
@@ -221,20 +223,12 @@ __device__ void ctrl_tail_beta(double* ctrl) {
   ctrl_store(ctrl + C_ITER, ctrl[C_ITER] + 1.0);
 }
 
-__device__ void ctrl_tail_combine(double* ctrl, double* out) {
-  out[0] = 0.5 * (ctrl_load(ctrl + C_DOT0) + ctrl_load(ctrl + C_DOT2));
-  out[1] = 0.5 * ctrl_load(ctrl + C_DOT2);
-  out[2] = ctrl_load(ctrl + C_DOT1);
-}
-
-__device__ __forceinline__ void run_ctrl_tail(int cf, double* ctrl,
-                                              double* out) {
+__device__ __forceinline__ void run_ctrl_tail(int cf, double* ctrl) {
   switch (cf) {
     case CF_Z0: ctrl_tail_z0(ctrl); break;
     case CF_ALPHA: ctrl_tail_alpha(ctrl); break;
     case CF_RR: ctrl_tail_rr(ctrl); break;
     case CF_BETA: ctrl_tail_beta(ctrl); break;
-    case CF_COMBINE: ctrl_tail_combine(ctrl, out); break;
     default: break;
   }
 }
@@ -258,6 +252,116 @@ __device__ __forceinline__ void block_reduce_atomic(double v, double* dst) {
   // the scratch is reused by back-to-back reductions in one kernel:
   // wave 0 must finish reading before anyone writes the next round
   __syncthreads();
+}
+
+// Epilogue of every fused reduction kernel: add this block's share of up
+// to three dots into their ctrl slots (a slot < 0 is skipped; the slot
+// tests are block-uniform), then — with a fused tail — fan in and let
+// the last block run the control tail. A kernel that staged data through
+// LDS must have put a barrier behind its last LDS read before calling.
+template <int CF>
+__device__ __forceinline__ void finish_reduction(double* ctrl,
+                                                 int slot0, double d0,
+                                                 int slot1 = -1,
+                                                 double d1 = 0.0,
+                                                 int slot2 = -1,
+                                                 double d2 = 0.0) {
+  if (slot0 >= 0) block_reduce_atomic(d0, ctrl + slot0);
+  if (slot1 >= 0) block_reduce_atomic(d1, ctrl + slot1);
+  if (slot2 >= 0) block_reduce_atomic(d2, ctrl + slot2);
+  if (CF != CF_NONE) {
+    if (fanin_last_block(ctrl) && threadIdx.x == 0) run_ctrl_tail(CF, ctrl);
+  }
+}
+
+// ---------------------------------------------------------------------
+// Per-pose building blocks shared by the kernels below. Each keeps one
+// fixed order of floating-point operations, so every kernel that uses it
+// produces the same bits for the same pose.
+// ---------------------------------------------------------------------
+// Tangent projection at X of one pose's dh x R tile held in registers:
+// S = sym(Y T^T) with Y the D Stiefel rows of Xi; T -= S Y on those rows
+// (the translation row is already tangent). Xi is read from memory: the
+// compiler keeps the D x R values it needs in registers by itself, and
+// an explicit register copy gave the same resource table.
+template <int D, int R>
+__device__ __forceinline__ void tangent_project(const double* Xi,
+                                                double (&T)[D + 1][R]) {
+  double S[D][D];
+  #pragma unroll
+  for (int a = 0; a < D; ++a)
+    #pragma unroll
+    for (int b = 0; b < D; ++b) {
+      double sv = 0.0;
+      #pragma unroll
+      for (int k = 0; k < R; ++k) sv = fma(Xi[a * R + k], T[b][k], sv);
+      S[a][b] = sv;
+    }
+  #pragma unroll
+  for (int a = 0; a < D; ++a)
+    #pragma unroll
+    for (int b = a; b < D; ++b) {
+      const double sv = 0.5 * (S[a][b] + S[b][a]);
+      S[a][b] = sv;
+      S[b][a] = sv;
+    }
+  #pragma unroll
+  for (int a = 0; a < D; ++a)
+    #pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double v = T[a][k];
+      #pragma unroll
+      for (int b = 0; b < D; ++b) v = fma(-S[a][b], Xi[b * R + k], v);
+      T[a][k] = v;
+    }
+}
+
+// The same projection for the element-per-thread kernels: the thread
+// owning element (c, k), c < D, of a pose whose X and T tiles sit in LDS
+// (row-major dh x R) returns its projected value; v is its own T(c, k).
+template <int D, int R>
+__device__ __forceinline__ double tangent_project_lds(const double* sX,
+                                                      const double* sT,
+                                                      int c, int k,
+                                                      double v) {
+  #pragma unroll
+  for (int b = 0; b < D; ++b) {
+    double s1 = 0.0, s2 = 0.0;
+    #pragma unroll
+    for (int kk = 0; kk < R; ++kk) {
+      s1 = fma(sX[c * R + kk], sT[b * R + kk], s1);
+      s2 = fma(sX[b * R + kk], sT[c * R + kk], s2);
+    }
+    v = fma(-0.5 * (s1 + s2), sX[b * R + k], v);
+  }
+  return v;
+}
+
+// One column of the per-pose block-Jacobi solve L L^T y = rhs with the
+// stored DH x DH Cholesky factor Li; rhs[a * stride] is row a.
+template <int DH>
+__device__ __forceinline__ void chol_solve_col(const double* Li,
+                                               const double* rhs,
+                                               size_t stride,
+                                               double (&y)[DH]) {
+  // forward solve L y = rhs
+  #pragma unroll
+  for (int a = 0; a < DH; ++a) {
+    double sv = rhs[a * stride];
+    #pragma unroll
+    for (int b = 0; b < DH; ++b)
+      if (b < a) sv = fma(-Li[a * DH + b], y[b], sv);
+    y[a] = sv / Li[a * DH + a];
+  }
+  // backward solve L^T z = y
+  #pragma unroll
+  for (int a = DH - 1; a >= 0; --a) {
+    double sv = y[a];
+    #pragma unroll
+    for (int b = 0; b < DH; ++b)
+      if (b > a) sv = fma(-Li[b * DH + a], y[b], sv);
+    y[a] = sv / Li[a * DH + a];
+  }
 }
 
 // ---------------------------------------------------------------------
@@ -328,7 +432,7 @@ __global__ void k_bsr_spmm_gen(const int* __restrict__ row_ptr,
 
 // ---------------------------------------------------------------------
 // Fused tangent projection + dots.
-//   P = V (+ G) projected onto T_X; optionally negate; write to out.
+//   P = V (+ G) projected onto T_X; write to out.
 //   Optional atomic dots: <P, dotWith> -> ctrl[dot_slot]
 //                         <V+G, X> -> ctrl[dot_slot2]   (for f(X))
 // One thread per pose; all of Yt (d x r), Vt (dh x r) live in registers
@@ -337,7 +441,7 @@ __global__ void k_bsr_spmm_gen(const int* __restrict__ row_ptr,
 #define DPO_MAX_R 8
 #define DPO_MAX_DH 4
 
-template <int NEG, int D, int R, int CF = CF_NONE>
+template <int D, int R, int CF = CF_NONE>
 __global__ void k_proj_dots(const double* __restrict__ X,
                             const double* __restrict__ V,
                             const double* __restrict__ G,
@@ -349,7 +453,6 @@ __global__ void k_proj_dots(const double* __restrict__ X,
   if (guarded_off(ctrl, guard)) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   constexpr int dh = D + 1;
-  double Yt[D][R];
   double Vt[dh][R];
   double dot_vx = 0.0;
   if (i < n) {
@@ -365,40 +468,7 @@ __global__ void k_proj_dots(const double* __restrict__ X,
         Vt[c][k] = v;
         if (dot_slot2 >= 0) dot_vx = fma(v, Xi[c * R + k], dot_vx);
       }
-    #pragma unroll
-    for (int c = 0; c < D; ++c)
-      #pragma unroll
-      for (int k = 0; k < R; ++k)
-        Yt[c][k] = Xi[c * R + k];
-    // S = sym(Yt Vt^T)  (D x D)
-    double S[D][D];
-    #pragma unroll
-    for (int a = 0; a < D; ++a)
-      #pragma unroll
-      for (int b = 0; b < D; ++b) {
-        double s = 0.0;
-        #pragma unroll
-        for (int k = 0; k < R; ++k) s = fma(Yt[a][k], Vt[b][k], s);
-        S[a][b] = s;
-      }
-    #pragma unroll
-    for (int a = 0; a < D; ++a)
-      #pragma unroll
-      for (int b = a; b < D; ++b) {
-        double s = 0.5 * (S[a][b] + S[b][a]);
-        S[a][b] = s;
-        S[b][a] = s;
-      }
-    // P = Vt - S Yt on Stiefel rows
-    #pragma unroll
-    for (int a = 0; a < D; ++a)
-      #pragma unroll
-      for (int k = 0; k < R; ++k) {
-        double acc = Vt[a][k];
-        #pragma unroll
-        for (int b = 0; b < D; ++b) acc = fma(-S[a][b], Yt[b][k], acc);
-        Vt[a][k] = acc;
-      }
+    tangent_project<D, R>(Xi, Vt);
   }
   double dot_pw = 0.0;
   if (i < n) {
@@ -408,20 +478,15 @@ __global__ void k_proj_dots(const double* __restrict__ X,
     for (int c = 0; c < dh; ++c)
       #pragma unroll
       for (int k = 0; k < R; ++k) {
-        double p = NEG ? -Vt[c][k] : Vt[c][k];
+        const double p = Vt[c][k];
         Oi[c * R + k] = p;
         if (dot_slot >= 0) {
-          double w = Wi ? Wi[c * R + k] : Vt[c][k];  // default: <P,P>
+          double w = Wi ? Wi[c * R + k] : p;  // default: <P,P>
           dot_pw = fma(p, w, dot_pw);
         }
       }
   }
-  if (dot_slot >= 0) block_reduce_atomic(dot_pw, ctrl + dot_slot);
-  if (dot_slot2 >= 0) block_reduce_atomic(dot_vx, ctrl + dot_slot2);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, nullptr);
-  }
+  finish_reduction<CF>(ctrl, dot_slot, dot_pw, dot_slot2, dot_vx);
 }
 
 // Fused block-Jacobi preconditioner apply + tangent projection (+ dot
@@ -444,7 +509,10 @@ __global__ void k_precond_proj(const double* __restrict__ L,
   if (i < n) {
     const double* Li = L + (size_t)i * dh * dh;
     const double* Ri = rvec + (size_t)i * dh * R;
-    // per-column forward/backward triangular solves (L L^T y = r)
+    // chol_solve_col and tangent_project written out, same operation
+    // order: through the helpers this kernel alone compiles to a
+    // different schedule (d = 3, r = 5: 92 instead of 114 VGPRs, fewer
+    // loads in flight) that measured 2.5-3.5 % slower per 1M-pose round.
     #pragma unroll
     for (int k = 0; k < R; ++k) {
       double y[dh];
@@ -467,7 +535,6 @@ __global__ void k_precond_proj(const double* __restrict__ L,
       #pragma unroll
       for (int a = 0; a < dh; ++a) Vt[a][k] = y[a];
     }
-    // tangent projection at X (Stiefel rows only)
     const double* Xi = X + (size_t)i * dh * R;
     double S[D][D];
     #pragma unroll
@@ -507,18 +574,14 @@ __global__ void k_precond_proj(const double* __restrict__ L,
           dot = fma(Vt[c][k], Ri[c * R + k], dot);
       }
   }
-  if (dot_slot >= 0) block_reduce_atomic(dot, ctrl + dot_slot);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, nullptr);
-  }
+  finish_reduction<CF>(ctrl, dot_slot, dot);
 }
 
 // Wide (element-per-thread) tangent projection for LARGE agents: same
 // wave-starvation fix as k_hess_wide (a thread-per-pose kernel gets
 // only n/64 waves). dh*r threads per pose; the cross-element sym(Y V^T)
 // contraction goes through LDS tiles.
-template <int NEG, int D, int R, int CF = CF_NONE>
+template <int D, int R, int CF = CF_NONE>
 __global__ void k_proj_wide(const double* __restrict__ X,
                             const double* __restrict__ V,
                             const double* __restrict__ G,
@@ -551,33 +614,17 @@ __global__ void k_proj_wide(const double* __restrict__ X,
   }
   __syncthreads();
   double o = v;
-  if (live && c < D) {
-    #pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double s1 = 0.0, s2 = 0.0;
-      #pragma unroll
-      for (int kk = 0; kk < R; ++kk) {
-        s1 = fma(sX[slot][c * R + kk], sV[slot][b * R + kk], s1);
-        s2 = fma(sX[slot][b * R + kk], sV[slot][c * R + kk], s2);
-      }
-      o = fma(-0.5 * (s1 + s2), sX[slot][b * R + k], o);
-    }
-  }
+  if (live && c < D)
+    o = tangent_project_lds<D, R>(sX[slot], sV[slot], c, k, v);
   if (live) {
-    const double p = NEG ? -o : o;
-    out[(size_t)i * TILE + e] = p;
+    out[(size_t)i * TILE + e] = o;
     if (dot_slot >= 0) {
       const double w = dotWith ? dotWith[(size_t)i * TILE + e] : o;
-      d0 = p * w;
+      d0 = o * w;
     }
   }
   __syncthreads();
-  if (dot_slot >= 0) block_reduce_atomic(d0, ctrl + dot_slot);
-  if (dot_slot2 >= 0) block_reduce_atomic(d1, ctrl + dot_slot2);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, nullptr);
-  }
+  finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1);
 }
 
 // ---------------------------------------------------------------------
@@ -666,35 +713,7 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
           for (int k = 0; k < R; ++k)
             d1 = fma(acc[c][k], Xi[c * R + k], d1);
       }
-      // tangent projection at X: S = sym(Yt A^T); A -= S Yt
-      double S[D][D];
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int b = 0; b < D; ++b) {
-          double sv = 0.0;
-          #pragma unroll
-          for (int k = 0; k < R; ++k)
-            sv = fma(Xi[a * R + k], acc[b][k], sv);
-          S[a][b] = sv;
-        }
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int b = a; b < D; ++b) {
-          const double sv = 0.5 * (S[a][b] + S[b][a]);
-          S[a][b] = sv;
-          S[b][a] = sv;
-        }
-      #pragma unroll
-      for (int a = 0; a < D; ++a)
-        #pragma unroll
-        for (int k = 0; k < R; ++k) {
-          double v = acc[a][k];
-          #pragma unroll
-          for (int b = 0; b < D; ++b) v = fma(-S[a][b], Xi[b * R + k], v);
-          acc[a][k] = v;
-        }
+      tangent_project<D, R>(Xi, acc);
       double* Oi = out + (size_t)i * dh * R;
       double* O2 = (AUX && out2) ? out2 + (size_t)i * dh * R : nullptr;
       const double* Wi = dotW ? dotW + (size_t)i * dh * R : nullptr;
@@ -717,14 +736,8 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
       }
     }
   }
-  if (dot_slot >= 0) block_reduce_atomic(d0, ctrl + dot_slot);
-  if (dot_slot2 >= 0) block_reduce_atomic(d1, ctrl + dot_slot2);
-  if (MODE == 0 && dot_slot3 >= 0)
-    block_reduce_atomic(d2, ctrl + dot_slot3);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, nullptr);
-  }
+  finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1,
+                       MODE == 0 ? dot_slot3 : -1, d2);
 }
 
 // ---------------------------------------------------------------------
@@ -794,18 +807,8 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
   if (MODE == 0) {
     __syncthreads();
     double o = acc;
-    if (live && c < D) {
-      #pragma unroll
-      for (int b = 0; b < D; ++b) {
-        double s1 = 0.0, s2 = 0.0;
-        #pragma unroll
-        for (int kk = 0; kk < R; ++kk) {
-          s1 = fma(sX[slot][c * R + kk], sAcc[slot][b * R + kk], s1);
-          s2 = fma(sX[slot][b * R + kk], sAcc[slot][c * R + kk], s2);
-        }
-        o = fma(-0.5 * (s1 + s2), sX[slot][b * R + k], o);
-      }
-    }
+    if (live && c < D)
+      o = tangent_project_lds<D, R>(sX[slot], sAcc[slot], c, k, acc);
     if (live) {
       out[(size_t)i * TILE + e] = o;
       if (AUX && out2) out2[(size_t)i * TILE + e] = o;
@@ -817,14 +820,8 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
     }
     __syncthreads();  // sAcc/sX reuse barrier for CF tail safety
   }
-  if (dot_slot >= 0) block_reduce_atomic(d0, ctrl + dot_slot);
-  if (dot_slot2 >= 0) block_reduce_atomic(d1, ctrl + dot_slot2);
-  if (MODE == 0 && dot_slot3 >= 0)
-    block_reduce_atomic(d2, ctrl + dot_slot3);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, nullptr);
-  }
+  finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1,
+                       MODE == 0 ? dot_slot3 : -1, d2);
 }
 
 // ---------------------------------------------------------------------
@@ -1080,26 +1077,9 @@ __global__ void k_precond_jacobi(const double* __restrict__ L,
   const int idx = blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n * r) return;
   const int i = idx / r, k = idx % r;
-  const double* Li = L + (size_t)i * DH * DH;
   double y[DH];
-  // forward solve L y = v
-  #pragma unroll
-  for (int a = 0; a < DH; ++a) {
-    double s = V[((size_t)i * DH + a) * r + k];
-    #pragma unroll
-    for (int b = 0; b < DH; ++b)
-      if (b < a) s = fma(-Li[a * DH + b], y[b], s);
-    y[a] = s / Li[a * DH + a];
-  }
-  // backward solve L^T z = y
-  #pragma unroll
-  for (int a = DH - 1; a >= 0; --a) {
-    double s = y[a];
-    #pragma unroll
-    for (int b = 0; b < DH; ++b)
-      if (b > a) s = fma(-Li[b * DH + a], y[b], s);
-    y[a] = s / Li[a * DH + a];
-  }
+  chol_solve_col<DH>(L + (size_t)i * DH * DH, V + (size_t)i * DH * r + k, r,
+                     y);
   #pragma unroll
   for (int a = 0; a < DH; ++a) Z[((size_t)i * DH + a) * r + k] = y[a];
 }
@@ -1154,11 +1134,7 @@ __global__ void k_tcg_update(double* __restrict__ eta,
       }
     }
   }
-  if (!stop_pending) block_reduce_atomic(rr, ctrl + C_DOT1);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, nullptr);
-  }
+  finish_reduction<CF>(ctrl, stop_pending ? -1 : C_DOT1, rr);
 }
 
 // delta = -z + beta * delta
@@ -1203,13 +1179,11 @@ __global__ void k_axpby(const double* __restrict__ A,
 }
 
 // dots: ctrl[slot] += <A, B>, optionally ctrl[slot2] += <A, C>
-template <int CF = CF_NONE>
 __global__ void k_dots(const double* __restrict__ A,
                        const double* __restrict__ B,
                        const double* __restrict__ C,
                        double* __restrict__ ctrl,
-                       int slot, int slot2, long total, int guard,
-                       double* __restrict__ cf_out = nullptr) {
+                       int slot, int slot2, long total, int guard) {
   if (guarded_off(ctrl, guard)) return;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   double d0 = 0.0, d1 = 0.0;
@@ -1220,10 +1194,6 @@ __global__ void k_dots(const double* __restrict__ A,
   }
   block_reduce_atomic(d0, ctrl + slot);
   if (C && slot2 >= 0) block_reduce_atomic(d1, ctrl + slot2);
-  if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0)
-      run_ctrl_tail(CF, ctrl, cf_out);
-  }
 }
 
 // ---------------------------------------------------------------------
@@ -1261,7 +1231,7 @@ __global__ void k_ctrl_init(double* ctrl, double tol, double Delta0,
 // the tail fused into that kernel's last block.
 template <int CF>
 __global__ void k_ctrl_tail(double* ctrl) {
-  if (threadIdx.x == 0) run_ctrl_tail(CF, ctrl, nullptr);
+  if (threadIdx.x == 0) run_ctrl_tail(CF, ctrl);
 }
 
 template <int CF>
@@ -1453,6 +1423,30 @@ __global__ void k_gnc_weights(const double* __restrict__ X,
   F(2, 2) F(2, 3) F(2, 4) F(2, 5) F(2, 6) \
   F(3, 3) F(3, 4) F(3, 5) F(3, 6) F(3, 7) F(3, 8)
 
+// Calls f(integral_constant<int, D>, integral_constant<int, R>) for the
+// supported pair equal to (d, r); false (f not called) for any other.
+// f is a generic lambda; its arguments convert to constant expressions
+// (constexpr int D = Dc), so it can name k_foo<D, R>.
+template <class F>
+static bool dispatch_dr(int d, int r, F&& f) {
+#define DPO_DISPATCH_ONE(D, R)                            \
+  if (d == D && r == R) {                                 \
+    f(std::integral_constant<int, D>{},                   \
+      std::integral_constant<int, R>{});                  \
+    return true;                                          \
+  }
+  DPO_FOREACH_DR(DPO_DISPATCH_ONE)
+#undef DPO_DISPATCH_ONE
+  return false;
+}
+
+// r alone, for kernels that do not depend on d: every r of the list.
+template <class F>
+static bool dispatch_r(int r, F&& f) {
+  auto g = [&](auto, auto Rc) { f(Rc); };
+  return dispatch_dr(2, r, g) || dispatch_dr(3, r, g);
+}
+
 static inline int blocks_for(long total, int bs) {
   return (int)((total + bs - 1) / bs);
 }
@@ -1468,71 +1462,12 @@ static void launch_spmm(const int* rp, const int* ci, const double* vals,
   const int dh = d + 1;
   const int tile = dh * r;
   const int grid = blocks_for(n, 256 / tile);
-#define CASE_SPMM(D, R) \
-  if (d == D && r == R) { \
-    hipLaunchKernelGGL((k_bsr_spmm<D + 1, R>), dim3(grid), dim3(256), 0, s, \
-                       rp, ci, vals, X, out, n, ctrl, guard); \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_SPMM)
-#undef CASE_SPMM
-  hipLaunchKernelGGL(k_bsr_spmm_gen, dim3(grid), dim3(256), 0, s,
-                     rp, ci, vals, X, out, n, dh, r, ctrl, guard);
-}
-
-static inline bool hess_use_wide(int n);
-
-template <int CF>
-static void launch_proj_dots_cf(const double* X, const double* V,
-                                const double* G, double* out,
-                                const double* dotWith, double* ctrl,
-                                int n, int d, int r, int dot_slot,
-                                int dot_slot2, int guard, hipStream_t s) {
-  const int grid = blocks_for(n, 256);
-  const bool wide = hess_use_wide(n);
-#define CASE_PROJ(D, R) \
-  if (d == D && r == R) { \
-    if (wide) { \
-      constexpr int PB = 256 / ((D + 1) * R); \
-      hipLaunchKernelGGL((k_proj_wide<0, D, R, CF>), \
-                         dim3(blocks_for(n, PB)), dim3(256), 0, s, \
-                         X, V, G, out, dotWith, ctrl, n, dot_slot, \
-                         dot_slot2, guard); \
-    } else { \
-      hipLaunchKernelGGL((k_proj_dots<0, D, R, CF>), dim3(grid), \
-                         dim3(256), 0, s, X, V, G, out, dotWith, ctrl, \
-                         n, dot_slot, dot_slot2, guard); \
-    } \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_PROJ)
-#undef CASE_PROJ
-  dpo_bad_shape(d, r);
-}
-
-static void launch_proj_dots(const double* X, const double* V,
-                             const double* G, double* out,
-                             const double* dotWith, double* ctrl,
-                             int n, int d, int r, int dot_slot,
-                             int dot_slot2, int guard, hipStream_t s) {
-  launch_proj_dots_cf<CF_NONE>(X, V, G, out, dotWith, ctrl, n, d, r,
-                               dot_slot, dot_slot2, guard, s);
-}
-
-static void launch_polar(const double* A, const double* B, const double* C,
-                         double ca, double cb, double cc, double* out,
-                         int n, int d, int r, const double* ctrl, int guard,
-                         hipStream_t s) {
-  const int grid = blocks_for(n, 256);
-#define CASE_POLAR(D, R) \
-  if (d == D && r == R) { \
-    hipLaunchKernelGGL((k_polar_affine<D, R>), dim3(grid), dim3(256), 0, s, \
-                       A, B, C, ca, cb, cc, out, n, ctrl, guard); \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_POLAR)
-#undef CASE_POLAR
-  dpo_bad_shape(d, r);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_bsr_spmm<Dc + 1, Rc>), dim3(grid), dim3(256),
+                           0, s, rp, ci, vals, X, out, n, ctrl, guard);
+      }))
+    hipLaunchKernelGGL(k_bsr_spmm_gen, dim3(grid), dim3(256), 0, s,
+                       rp, ci, vals, X, out, n, dh, r, ctrl, guard);
 }
 
 // Wide-variant selection: element-per-thread (dh*r threads per pose)
@@ -1554,6 +1489,43 @@ static inline bool hess_use_wide(int n) {
   return false;
 }
 
+template <int CF = CF_NONE>
+static void launch_proj_dots(const double* X, const double* V,
+                             const double* G, double* out,
+                             const double* dotWith, double* ctrl,
+                             int n, int d, int r, int dot_slot,
+                             int dot_slot2, int guard, hipStream_t s) {
+  const bool wide = hess_use_wide(n);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        constexpr int D = Dc, R = Rc;
+        if (wide) {
+          constexpr int PB = 256 / ((D + 1) * R);
+          hipLaunchKernelGGL((k_proj_wide<D, R, CF>),
+                             dim3(blocks_for(n, PB)), dim3(256), 0, s,
+                             X, V, G, out, dotWith, ctrl, n, dot_slot,
+                             dot_slot2, guard);
+        } else {
+          hipLaunchKernelGGL((k_proj_dots<D, R, CF>),
+                             dim3(blocks_for(n, 256)), dim3(256), 0, s,
+                             X, V, G, out, dotWith, ctrl, n, dot_slot,
+                             dot_slot2, guard);
+        }
+      }))
+    dpo_bad_shape(d, r);
+}
+
+static void launch_polar(const double* A, const double* B, const double* C,
+                         double ca, double cb, double cc, double* out,
+                         int n, int d, int r, const double* ctrl, int guard,
+                         hipStream_t s) {
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_polar_affine<Dc, Rc>),
+                           dim3(blocks_for(n, 256)), dim3(256), 0, s,
+                           A, B, C, ca, cb, cc, out, n, ctrl, guard);
+      }))
+    dpo_bad_shape(d, r);
+}
+
 template <int MODE, int CF = CF_NONE, int AUX = 0>
 static void launch_hess_fused(const int* rp, const int* ci,
                               const double* vals, const double* V,
@@ -1564,29 +1536,25 @@ static void launch_hess_fused(const int* rp, const int* ci,
                               hipStream_t s, int dot_slot3 = -1,
                               double* out2 = nullptr,
                               double* zero_out = nullptr) {
-  const int grid = blocks_for(n, 256);
   const bool wide = hess_use_wide(n);
-#define CASE_HF(D, R) \
-  if (d == D && r == R) { \
-    if (wide) { \
-      constexpr int PB = 256 / ((D + 1) * R); \
-      hipLaunchKernelGGL((k_hess_wide<D, R, MODE, CF, AUX>), \
-                         dim3(blocks_for(n, PB)), dim3(256), 0, s, \
-                         rp, ci, vals, V, X, G, out, dotW, \
-                         ctrl, n, dot_slot, dot_slot2, dot_slot3, \
-                         guard, out2, zero_out); \
-    } else { \
-      hipLaunchKernelGGL((k_hess_fused<D, R, MODE, CF, AUX>), \
-                         dim3(grid), \
-                         dim3(256), 0, s, rp, ci, vals, V, X, G, out, \
-                         dotW, ctrl, n, dot_slot, dot_slot2, dot_slot3, \
-                         guard, out2, zero_out); \
-    } \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_HF)
-#undef CASE_HF
-  dpo_bad_shape(d, r);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        constexpr int D = Dc, R = Rc;
+        if (wide) {
+          constexpr int PB = 256 / ((D + 1) * R);
+          hipLaunchKernelGGL((k_hess_wide<D, R, MODE, CF, AUX>),
+                             dim3(blocks_for(n, PB)), dim3(256), 0, s,
+                             rp, ci, vals, V, X, G, out, dotW, ctrl, n,
+                             dot_slot, dot_slot2, dot_slot3, guard, out2,
+                             zero_out);
+        } else {
+          hipLaunchKernelGGL((k_hess_fused<D, R, MODE, CF, AUX>),
+                             dim3(blocks_for(n, 256)), dim3(256), 0, s,
+                             rp, ci, vals, V, X, G, out, dotW, ctrl, n,
+                             dot_slot, dot_slot2, dot_slot3, guard, out2,
+                             zero_out);
+        }
+      }))
+    dpo_bad_shape(d, r);
 }
 
 // Graph-safe zero / device->pinned-host copy. hipMemsetAsync and
@@ -1602,6 +1570,11 @@ __global__ void k_ctrl_to_host(const double* __restrict__ src,
                                double* __restrict__ dst, int n) {
   int i = threadIdx.x;
   if (i < n) dst[i] = src[i];
+}
+
+static inline void dzero(double* p, long n, hipStream_t s) {
+  hipLaunchKernelGGL(k_dzero, dim3(blocks_for(n, 256)), dim3(256), 0, s, p,
+                     n);
 }
 
 // j-split so small problems still produce >= ~512 workgroups
@@ -1621,21 +1594,14 @@ static void launch_precond_dense(const float* Minv, const double* V,
                                  hipStream_t s, bool prezeroed = false) {
   const int gx = blocks_for(N, 256);
   const int jsplit = precond_dense_jsplit(N);
-  if (jsplit > 1 && !prezeroed) {
-    // kernel (not hipMemsetAsync): this runs inside captured graphs,
-    // which must stay free of SDMA nodes (see fence comment)
-    hipLaunchKernelGGL(k_dzero, dim3(blocks_for((long)N * r, 256)),
-                       dim3(256), 0, s, Z, (long)N * r);
-  }
-#define CASE_PD(D, R) \
-  if (r == R) { \
-    hipLaunchKernelGGL((k_precond_dense<R>), dim3(gx, jsplit), dim3(256), \
-                       0, s, Minv, V, Z, N, ctrl, guard); \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_PD)
-#undef CASE_PD
-  dpo_bad_shape(-1, r);
+  // kernel (not hipMemsetAsync): this runs inside captured graphs,
+  // which must stay free of SDMA nodes (see fence comment)
+  if (jsplit > 1 && !prezeroed) dzero(Z, (long)N * r, s);
+  if (!dispatch_r(r, [&](auto Rc) {
+        hipLaunchKernelGGL((k_precond_dense<Rc>), dim3(gx, jsplit),
+                           dim3(256), 0, s, Minv, V, Z, N, ctrl, guard);
+      }))
+    dpo_bad_shape(-1, r);
 }
 
 static void launch_precond_jacobi(const double* L, const double* V,
@@ -1651,6 +1617,17 @@ static void launch_precond_jacobi(const double* L, const double* V,
                        L, V, Z, n, r, ctrl, guard);
   else
     dpo_bad_shape(dh - 1, r);
+}
+
+template <int CF>
+static void launch_tcg_update(double* eta, double* rvec, const double* delta,
+                              const double* Hd, double* eta_snap,
+                              double* delta_snap, double* ctrl, long total,
+                              double* zero_out, hipStream_t s) {
+  hipLaunchKernelGGL((k_tcg_update<CF>),
+                     dim3(blocks_for((total + 3) / 4, 256)), dim3(256), 0, s,
+                     eta, rvec, delta, Hd, eta_snap, delta_snap, ctrl, total,
+                     zero_out);
 }
 
 extern "C" {
@@ -1707,11 +1684,8 @@ void dpo_precond_jacobi(const double* L, const double* V, double* Z,
 void dpo_tcg_update(double* eta, double* rvec, const double* delta,
                     const double* Hd, double* eta_snap, double* delta_snap,
                     double* ctrl, long total, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((k_tcg_update<CF_NONE>),
-                     dim3(blocks_for((total + 3) / 4, 256)),
-                     dim3(256), 0, s, eta, rvec, delta, Hd, eta_snap,
-                     delta_snap, ctrl, total, (double*)nullptr);
+  launch_tcg_update<CF_NONE>(eta, rvec, delta, Hd, eta_snap, delta_snap,
+                             ctrl, total, nullptr, (hipStream_t)stream);
 }
 
 void dpo_tcg_delta(double* delta, const double* z, double* ctrl, long total,
@@ -1740,9 +1714,8 @@ void dpo_dots(const double* A, const double* B, const double* C,
               double* ctrl, int slot, int slot2, long total, int guard,
               void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((k_dots<CF_NONE>), dim3(blocks_for(total, 256)),
-                     dim3(256), 0, s, A, B, C, ctrl, slot, slot2, total,
-                     guard, (double*)nullptr);
+  hipLaunchKernelGGL(k_dots, dim3(blocks_for(total, 256)), dim3(256), 0, s,
+                     A, B, C, ctrl, slot, slot2, total, guard);
 }
 
 void dpo_ctrl_init(double* ctrl, double tol, double Delta0, double theta,
@@ -1809,18 +1782,14 @@ void dpo_gnc_weights(const double* X, const double* nbr, const long* e1_idx,
                      const long* widx, double* weights, int ne, int d,
                      int r, double mu, double barc_sq, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const int grid = blocks_for(ne, 256);
-#define CASE_GNC(D, R) \
-  if (d == D && r == R) { \
-    hipLaunchKernelGGL((k_gnc_weights<D, R>), dim3(grid), dim3(256), 0, s, \
-                       X, nbr, e1_idx, e1_nbr, e2_idx, e2_nbr, Rm, tm, \
-                       kappa, tau, update_mask, widx, weights, ne, mu, \
-                       barc_sq); \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_GNC)
-#undef CASE_GNC
-  dpo_bad_shape(d, r);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_gnc_weights<Dc, Rc>),
+                           dim3(blocks_for(ne, 256)), dim3(256), 0, s,
+                           X, nbr, e1_idx, e1_nbr, e2_idx, e2_nbr, Rm, tm,
+                           kappa, tau, update_mask, widx, weights, ne, mu,
+                           barc_sq);
+      }))
+    dpo_bad_shape(d, r);
 }
 
 }  // extern "C"
@@ -2025,11 +1994,6 @@ static inline void fence_wait(DpoCtx* c, int which, hipStream_t s) {
                      c->fences + which);
 }
 
-static inline void dzero(double* p, long n, hipStream_t s) {
-  hipLaunchKernelGGL(k_dzero, dim3((unsigned)((n + 255) / 256)), dim3(256),
-                     0, s, p, n);
-}
-
 static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s) {
   if (c->g_ne == 0) { c->Gt = nullptr; return; }
   dzero(c->G_buf, c->total, s);
@@ -2060,33 +2024,17 @@ static void ctx_precond(DpoCtx* c, const double* V, double* Z,
                           ST_RUN, s);
 }
 
-// Fused z-stage: z = P_X(M^-1 r) + <z, r> dot + CF tail in one kernel
-// when the block-Jacobi preconditioner is active (large agents);
-// otherwise the dense apply runs standalone followed by the fused
-// projection kernel, as before.
-template <int CF>
-static void ctx_precond_proj(DpoCtx* c, const double* X, hipStream_t s) {
-  if (c->Minv == nullptr) {
-    const int grid = blocks_for(c->n, 256);
-#define CASE_PP(D, R) \
-    if (c->d == D && c->r == R) { \
-      hipLaunchKernelGGL((k_precond_proj<D, R, CF>), dim3(grid), \
-                         dim3(256), 0, s, c->Ljac, c->rvec, X, c->z, \
-                         c->ctrl, c->n, C_DOT0, ST_RUN); \
-      return; \
-    }
-    DPO_FOREACH_DR(CASE_PP)
-#undef CASE_PP
-  }
-  ctx_precond(c, c->rvec, c->z, s);
-  launch_proj_dots_cf<CF>(X, c->z, nullptr, c->z, c->rvec, c->ctrl,
-                          c->n, c->d, c->r, C_DOT0, -1, ST_RUN, s);
-}
-
-static void ctx_spmm(DpoCtx* c, const double* X, double* out, int guard,
-                     hipStream_t s) {
-  launch_spmm(c->q_rp, c->q_ci, c->q_vals, c->n, c->d, c->r, X, out,
-              c->ctrl, guard, s);
+// k_hess_fused / k_hess_wide on the bound problem's Q.
+template <int MODE, int CF = CF_NONE, int AUX = 0>
+static void ctx_hess(DpoCtx* c, const double* V, const double* X,
+                     const double* G, double* out, const double* dotW,
+                     int dot_slot, int dot_slot2, int guard, hipStream_t s,
+                     int dot_slot3 = -1, double* out2 = nullptr,
+                     double* zero_out = nullptr) {
+  launch_hess_fused<MODE, CF, AUX>(c->q_rp, c->q_ci, c->q_vals, V, X, G, out,
+                                   dotW, c->ctrl, c->n, c->d, c->r, dot_slot,
+                                   dot_slot2, guard, s, dot_slot3, out2,
+                                   zero_out);
 }
 
 extern "C" {
@@ -2162,6 +2110,8 @@ void dpo_ctx_set_problem(void* h, const int* rp, const int* ci,
   c->Gt = Gt; c->Minv = Minv; c->Ljac = Ljac;
 }
 
+}  // extern "C"
+
 // DPO_TCG_SEG=K: tCG iterations in the primary solve graph. The solve
 // graph is static, so every iteration it holds is launched whether or
 // not tCG has already stopped (a stopped iteration is 5-6 guarded no-op
@@ -2203,12 +2153,64 @@ static bool solve_no_cf() {
   return no_cf;
 }
 
+// One reduction stage of the solve: launch(cf) enqueues its kernel with
+// the control tail cf (an integral_constant) fused in — the stage's own
+// tail CF by default; with DPO_NO_CF=1, CF_NONE followed by the tail's
+// standalone launch.
+template <int CF, class Launch>
+static void enqueue_with_tail(DpoCtx* c, hipStream_t s, Launch launch) {
+  if (solve_no_cf()) {
+    launch(std::integral_constant<int, CF_NONE>{});
+    launch_ctrl_tail<CF>(c->ctrl, s);
+  } else {
+    launch(std::integral_constant<int, CF>{});
+  }
+}
+
+// Hd stage: Hd = P_X(Q delta), <delta, Hd>, alpha / boundary decision.
+static void enqueue_hd_stage(DpoCtx* c, const double* X, hipStream_t s) {
+  enqueue_with_tail<CF_ALPHA>(c, s, [&](auto cf) {
+    ctx_hess<0, cf>(c, c->delta, X, nullptr, c->Hd, c->delta, C_DOT0, -1,
+                    ST_RUN, s);
+  });
+}
+
+// Update stage: snapshots, eta and residual updates, ||r||^2, stop test.
+// Clears ctx_prezero_z(c) for the dense apply of the z stage behind it.
+static void enqueue_update_stage(DpoCtx* c, hipStream_t s) {
+  enqueue_with_tail<CF_RR>(c, s, [&](auto cf) {
+    launch_tcg_update<cf>(c->eta, c->rvec, c->delta, c->Hd, c->eta_snap,
+                          c->delta_snap, c->ctrl, c->total,
+                          ctx_prezero_z(c), s);
+  });
+}
+
+// z stage: z = P_X(M^-1 r), <z, r>, then the tail CF (CF_Z0 for z0,
+// CF_BETA in the loop). Block-Jacobi (large agents) does all of it in
+// one k_precond_proj launch; the dense apply runs standalone in front of
+// the projection kernel, and so does the Jacobi apply under DPO_NO_CF=1.
+template <int CF>
+static void enqueue_z_stage(DpoCtx* c, const double* X, hipStream_t s) {
+  if (!c->Minv && !solve_no_cf()) {
+    if (!dispatch_dr(c->d, c->r, [&](auto Dc, auto Rc) {
+          hipLaunchKernelGGL((k_precond_proj<Dc, Rc, CF>),
+                             dim3(blocks_for(c->n, 256)), dim3(256), 0, s,
+                             c->Ljac, c->rvec, X, c->z, c->ctrl, c->n,
+                             C_DOT0, ST_RUN);
+        }))
+      dpo_bad_shape(c->d, c->r);
+    return;
+  }
+  ctx_precond(c, c->rvec, c->z, s);
+  enqueue_with_tail<CF>(c, s, [&](auto cf) {
+    launch_proj_dots<cf>(X, c->z, nullptr, c->z, c->rvec, c->ctrl, c->n,
+                         c->d, c->r, C_DOT0, -1, ST_RUN, s);
+  });
+}
+
 // Head: G assembly, gradient, control init, z0 and the first delta.
 static void enqueue_solve_head(DpoCtx* c, double* X, const double* nbr,
                                double tol, double Delta0, hipStream_t s) {
-  const int n = c->n, d = c->d, r = c->r;
-  const long total = c->total;
-  const int gvec = (int)((total + 255) / 256);
   fence_wait(c, F_SOLVE_IN, s);  // first node: block until inputs ready
   if (nbr) ctx_assemble_g(c, nbr, s);
   dzero(c->ctrl, CTRL_SIZE, s);
@@ -2218,24 +2220,12 @@ static void enqueue_solve_head(DpoCtx* c, double* X, const double* nbr,
   // two-kernel split re-read the full iterate from HBM). It writes the
   // gradient to grad and to rvec (the tCG residual starts as the
   // gradient) and clears z for the z0 dense apply.
-  launch_hess_fused<0, CF_NONE, 1>(
-      c->q_rp, c->q_ci, c->q_vals, X, X, c->Gt, c->grad, nullptr,
-      c->ctrl, n, d, r, C_DOT1, C_DOT0, -1, s,
-      c->Gt ? C_DOT2 : -1,  // <G,X> folded in
-      c->rvec, ctx_prezero_z(c));
-  hipLaunchKernelGGL(k_ctrl_init, dim3(1), dim3(64), 0, s, c->ctrl, tol,
-                     Delta0, 1.0, 0.1);
-  // z0
-  if (solve_no_cf()) {
-    ctx_precond(c, c->rvec, c->z, s);
-    launch_proj_dots(X, c->z, nullptr, c->z, c->rvec, c->ctrl, n, d, r,
-                     C_DOT0, -1, ST_RUN, s);
-    launch_ctrl_tail<CF_Z0>(c->ctrl, s);
-  } else {
-    ctx_precond_proj<CF_Z0>(c, X, s);
-  }
-  hipLaunchKernelGGL(k_tcg_delta, dim3(gvec), dim3(256), 0, s,
-                     c->delta, c->z, c->ctrl, total);
+  ctx_hess<0, CF_NONE, 1>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0,
+                          -1, s, c->Gt ? C_DOT2 : -1,  // <G,X> folded in
+                          c->rvec, ctx_prezero_z(c));
+  dpo_ctrl_init(c->ctrl, tol, Delta0, 1.0, 0.1, s);
+  enqueue_z_stage<CF_Z0>(c, X, s);
+  dpo_tcg_delta(c->delta, c->z, c->ctrl, c->total, s);
 }
 
 // `count` tCG iterations. Position-independent: every kernel reads the
@@ -2243,68 +2233,41 @@ static void enqueue_solve_head(DpoCtx* c, double* X, const double* nbr,
 // the status is ST_RUN.
 static void enqueue_tcg_iters(DpoCtx* c, double* X, int count,
                               hipStream_t s) {
-  const int n = c->n, d = c->d, r = c->r;
-  const long total = c->total;
-  const int gvec = (int)((total + 255) / 256);
-  const bool no_cf = solve_no_cf();
-  double* zero_z = ctx_prezero_z(c);  // cleared for the next dense apply
   for (int j = 0; j < count; ++j) {
-    if (no_cf) {
-      launch_hess_fused<0>(c->q_rp, c->q_ci, c->q_vals, c->delta, X,
-                           nullptr, c->Hd, c->delta, c->ctrl, n, d, r,
-                           C_DOT0, -1, ST_RUN, s);
-      launch_ctrl_tail<CF_ALPHA>(c->ctrl, s);
-      hipLaunchKernelGGL((k_tcg_update<CF_NONE>),
-                         dim3(blocks_for((total + 3) / 4, 256)),
-                         dim3(256), 0, s, c->eta, c->rvec, c->delta,
-                         c->Hd, c->eta_snap, c->delta_snap, c->ctrl,
-                         total, zero_z);
-      launch_ctrl_tail<CF_RR>(c->ctrl, s);
-    } else {
-      launch_hess_fused<0, CF_ALPHA>(
-          c->q_rp, c->q_ci, c->q_vals, c->delta, X, nullptr, c->Hd,
-          c->delta, c->ctrl, n, d, r, C_DOT0, -1, ST_RUN, s);
-      hipLaunchKernelGGL((k_tcg_update<CF_RR>),
-                         dim3(blocks_for((total + 3) / 4, 256)),
-                         dim3(256), 0, s, c->eta, c->rvec, c->delta,
-                         c->Hd, c->eta_snap, c->delta_snap, c->ctrl,
-                         total, zero_z);
-    }
-    if (no_cf) {
-      ctx_precond(c, c->rvec, c->z, s);
-      launch_proj_dots(X, c->z, nullptr, c->z, c->rvec, c->ctrl, n, d, r,
-                       C_DOT0, -1, ST_RUN, s);
-      launch_ctrl_tail<CF_BETA>(c->ctrl, s);
-    } else {
-      ctx_precond_proj<CF_BETA>(c, X, s);
-    }
-    hipLaunchKernelGGL(k_tcg_delta, dim3(gvec), dim3(256), 0, s,
-                       c->delta, c->z, c->ctrl, total);
+    enqueue_hd_stage(c, X, s);
+    enqueue_update_stage(c, s);
+    enqueue_z_stage<CF_BETA>(c, X, s);
+    dpo_tcg_delta(c->delta, c->z, c->ctrl, c->total, s);
   }
 }
 
-// Tail: first candidate + acceptance test, control block to the host.
-// Every kernel but the copy is guarded by ST_TCG_STOP, so behind a
-// segment that left tCG running the tail is a no-op and the host reads
-// ST_RUN.
-static void enqueue_solve_tail(DpoCtx* c, double* X, double accept_rho,
-                               hipStream_t s) {
-  const int n = c->n, d = c->d, r = c->r;
-  const long total = c->total;
-  const int gvec = (int)((total + 255) / 256);
-  hipLaunchKernelGGL(k_ctrl_candidate, dim3(1), dim3(64), 0, s, c->ctrl);
-  hipLaunchKernelGGL(k_form_step, dim3(gvec), dim3(256), 0, s,
-                     c->step, c->eta, c->eta_snap, c->delta_snap,
-                     c->ctrl, total);
-  launch_polar(X, c->step, nullptr, 1.0, 1.0, 0.0, c->Xprop, n, d, r,
-               c->ctrl, ST_TCG_STOP, s);
-  launch_hess_fused<1>(c->q_rp, c->q_ci, c->q_vals, c->Xprop, nullptr,
-                       c->Gt, nullptr, nullptr, c->ctrl, n, d, r,
-                       C_DOT0, C_DOT2, ST_TCG_STOP, s);
-  hipLaunchKernelGGL(k_ctrl_accept, dim3(1), dim3(64), 0, s, c->ctrl,
-                     accept_rho);
+// One trust-region candidate at the current radius: pick the step from
+// the stored Krylov path, retract, evaluate f, run the acceptance test.
+// Every kernel is guarded by ST_TCG_STOP.
+static void enqueue_candidate(DpoCtx* c, const double* X, double accept_rho,
+                              hipStream_t s) {
+  dpo_ctrl_candidate(c->ctrl, s);
+  dpo_form_step(c->step, c->eta, c->eta_snap, c->delta_snap, c->ctrl,
+                c->total, s);
+  launch_polar(X, c->step, nullptr, 1.0, 1.0, 0.0, c->Xprop, c->n, c->d,
+               c->r, c->ctrl, ST_TCG_STOP, s);
+  ctx_hess<1>(c, c->Xprop, nullptr, c->Gt, nullptr, nullptr, C_DOT0, C_DOT2,
+              ST_TCG_STOP, s);
+  dpo_ctrl_accept(c->ctrl, accept_rho, s);
+}
+
+static void ctx_ctrl_to_host(DpoCtx* c, hipStream_t s) {
   hipLaunchKernelGGL(k_ctrl_to_host, dim3(1), dim3(64), 0, s, c->ctrl,
                      c->ctrl_host_dev, CTRL_SIZE);
+}
+
+// Tail: first candidate + acceptance test, control block to the host.
+// Behind a segment that left tCG running the candidate is a no-op and
+// the host reads ST_RUN.
+static void enqueue_solve_tail(DpoCtx* c, double* X, double accept_rho,
+                               hipStream_t s) {
+  enqueue_candidate(c, X, accept_rho, s);
+  ctx_ctrl_to_host(c, s);
   fence_signal(c, F_SOLVE_OUT, s);  // last node: mark sequence complete
 }
 
@@ -2317,8 +2280,7 @@ static void enqueue_solve_body(DpoCtx* c, double* X, const double* nbr,
                                hipStream_t s) {
   enqueue_solve_head(c, X, nbr, tol, Delta0, s);
   enqueue_tcg_iters(c, X, iters, s);
-  if (iters >= c->max_inner)
-    hipLaunchKernelGGL(k_ctrl_tcg_end, dim3(1), dim3(64), 0, s, c->ctrl);
+  if (iters >= c->max_inner) dpo_ctrl_tcg_end(c->ctrl, s);
   enqueue_solve_tail(c, X, accept_rho, s);
 }
 
@@ -2327,14 +2289,10 @@ static void enqueue_solve_cont(DpoCtx* c, double* X, double accept_rho,
                                int done, hipStream_t s) {
   fence_wait(c, F_SOLVE_IN, s);
   enqueue_tcg_iters(c, X, c->max_inner - done, s);
-  hipLaunchKernelGGL(k_ctrl_tcg_end, dim3(1), dim3(64), 0, s, c->ctrl);
+  dpo_ctrl_tcg_end(c->ctrl, s);
   enqueue_solve_tail(c, X, accept_rho, s);
 }
 
-// Full RBCD local solve in place on X. stats_out (host, >= 8 doubles):
-// [status, f_init, gn_init, f_opt, gn_opt, rho, shrink_count, iters]
-// nbr != null: assemble G from the packed neighbor buffer first; the
-// whole pre-sync sequence is then served from a cached hipGraph.
 // Ensure the solve graph for (X, nbr, tol, Delta0) is cached; run the
 // pre-sync sequence (via graph replay or eagerly) on stream s WITHOUT
 // the final synchronize. Returns true when the sequence was enqueued
@@ -2406,35 +2364,20 @@ static bool solve_continue(DpoCtx* c, double* X, const double* nbr,
 static int solve_postsync(DpoCtx* c, double* X, double accept_rho,
                           int max_shrink, int compute_final_gn,
                           double* stats_out, hipStream_t s) {
-  const int n = c->n, d = c->d, r = c->r;
-  const long total = c->total;
-  const int gvec = (int)((total + 255) / 256);
   int st = (int)c->ctrl_host[C_STATUS];
   if (st == ST_TCG_STOP && max_shrink > 0) {
     for (int attempt = 1; attempt <= max_shrink; ++attempt) {
-      hipLaunchKernelGGL(k_ctrl_shrink, dim3(1), dim3(64), 0, s, c->ctrl);
-      hipLaunchKernelGGL(k_ctrl_candidate, dim3(1), dim3(64), 0, s,
-                         c->ctrl);
-      hipLaunchKernelGGL(k_form_step, dim3(gvec), dim3(256), 0, s,
-                         c->step, c->eta, c->eta_snap, c->delta_snap,
-                         c->ctrl, total);
-      launch_polar(X, c->step, nullptr, 1.0, 1.0, 0.0, c->Xprop, n, d, r,
-                   c->ctrl, ST_TCG_STOP, s);
-      launch_hess_fused<1>(c->q_rp, c->q_ci, c->q_vals, c->Xprop, nullptr,
-                           c->Gt, nullptr, nullptr, c->ctrl, n, d, r,
-                           C_DOT0, C_DOT2, ST_TCG_STOP, s);
-      hipLaunchKernelGGL(k_ctrl_accept, dim3(1), dim3(64), 0, s, c->ctrl,
-                         accept_rho);
+      dpo_ctrl_shrink(c->ctrl, s);
+      enqueue_candidate(c, X, accept_rho, s);
     }
-    hipLaunchKernelGGL(k_ctrl_to_host, dim3(1), dim3(64), 0, s, c->ctrl,
-                       c->ctrl_host_dev, CTRL_SIZE);
+    ctx_ctrl_to_host(c, s);
     DPO_CHECK(hipStreamSynchronize(s));
     st = (int)c->ctrl_host[C_STATUS];
   }
   const int shrinks = (int)c->ctrl_host[C_SHRINKS];
   int status = st;
   if (st == ST_ACCEPTED) {
-    DPO_CHECK(hipMemcpyAsync(X, c->Xprop, total * sizeof(double),
+    DPO_CHECK(hipMemcpyAsync(X, c->Xprop, c->total * sizeof(double),
                              hipMemcpyDeviceToDevice, s));
   } else if (st == ST_TCG_STOP) {
     status = ST_GIVE_UP;  // every radius rejected: keep the iterate
@@ -2446,9 +2389,7 @@ static int solve_postsync(DpoCtx* c, double* X, double accept_rho,
   double gn_opt = gn_init;
   if (compute_final_gn && status == ST_ACCEPTED) {
     DPO_CHECK(hipMemsetAsync(c->ctrl + C_DOT1, 0, sizeof(double), s));
-    launch_hess_fused<0>(c->q_rp, c->q_ci, c->q_vals, X, X, c->Gt,
-                         c->grad, nullptr, c->ctrl, n, d, r, C_DOT1, -1,
-                         -1, s);
+    ctx_hess<0>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, -1, -1, s);
     DPO_CHECK(hipMemcpyAsync(c->ctrl_host + C_DOT1, c->ctrl + C_DOT1,
                              sizeof(double), hipMemcpyDeviceToHost, s));
     DPO_CHECK(hipStreamSynchronize(s));
@@ -2472,6 +2413,10 @@ static int solve_postsync(DpoCtx* c, double* X, double accept_rho,
   return status;
 }
 
+// Full RBCD local solve in place on X. stats_out (host, >= 8 doubles):
+// [status, f_init, gn_init, f_opt, gn_opt, rho, shrink_count, hlen].
+// nbr != null: assemble G from the packed neighbor buffer first; the
+// whole pre-sync sequence is then served from a cached hipGraph.
 static int rbcd_solve_impl(DpoCtx* c, double* X, const double* nbr,
                            double tol, double Delta0, int max_shrink,
                            double accept_rho, int compute_final_gn,
@@ -2485,6 +2430,8 @@ static int rbcd_solve_impl(DpoCtx* c, double* X, const double* nbr,
                         stats_out, s);
 }
 
+extern "C" {
+
 int dpo_rbcd_solve(void* h, double* X, double tol, double Delta0,
                    int max_shrink, double accept_rho,
                    int compute_final_gn, double* stats_out, void* stream) {
@@ -2492,12 +2439,6 @@ int dpo_rbcd_solve(void* h, double* X, double tol, double Delta0,
                          accept_rho, compute_final_gn, stats_out,
                          (hipStream_t)stream);
 }
-
-void dpo_round_eval(void* h, const double* X, const double* nbr,
-                    double* out_dev, void* stream);  // fwd decl
-static void round_eval_impl(DpoCtx* c, const double* X, const double* nbr,
-                            double* out_dev, hipStream_t s,
-                            bool wait_out = true);  // fwd decl
 
 // --- async (multi-stream) round entry points ------------------------
 // Launch the solve's pre-sync sequence on the ctx's private execution
@@ -2552,13 +2493,13 @@ int dpo_round_solve_finish(void* h, int max_shrink, double* stats_out,
                            (hipStream_t)join_stream);
 }
 
-// out[0] = solves, out[1] = continuation launches, out[2 + h] = solves
-// that ended with C_HLEN == h (h = 0 .. MAX_TCG). Writes at most `cap`
-// entries; returns the full length.
 // tCG iterations in the primary solve graph of this context, for the
 // problem currently bound (DPO_TCG_SEG resolved); == max_inner: one graph.
 int dpo_tcg_segment(void* h) { return solve_segment((DpoCtx*)h); }
 
+// out[0] = solves, out[1] = continuation launches, out[2 + h] = solves
+// that ended with C_HLEN == h (h = 0 .. MAX_TCG). Writes at most `cap`
+// entries; returns the full length.
 int dpo_ctx_counters(void* h, long* out, int cap) {
   DpoCtx* c = (DpoCtx*)h;
   const int len = 2 + MAX_TCG + 1;
@@ -2568,37 +2509,20 @@ int dpo_ctx_counters(void* h, long* out, int cap) {
   return len;
 }
 
-void dpo_round_eval_async(void* h, const double* X, const double* nbr,
-                          double* out_dev, void* join_stream) {
-  DpoCtx* c = (DpoCtx*)h;
-  hipStream_t js = (hipStream_t)join_stream;
-  // IN fence on the producer stream: carries the boundary-pose scatter
-  fence_signal(c, F_EVAL_IN, js);
-  round_eval_impl(c, X, nbr, out_dev, c->exec_stream, true);
-  DPO_CHECK(hipEventRecord(c->done_event, c->exec_stream));
-}
-
-void dpo_eval_join(void* h, void* join_stream) {
-  DpoCtx* c = (DpoCtx*)h;
-  DPO_CHECK(hipStreamWaitEvent((hipStream_t)join_stream, c->done_event, 0));
-}
-
 // Per-round evaluation: out_dev (>=3 doubles, device) = [f, 0.5<X,G>, gn2]
 // using the ctx's problem pointers. No host sync.
 void dpo_eval_terms(void* h, const double* X, double* out_dev,
                     void* stream) {
   DpoCtx* c = (DpoCtx*)h;
   hipStream_t s = (hipStream_t)stream;
-  const int n = c->n, d = c->d, r = c->r;
   // dot slots are pre-zeroed (zero-init at allocation; k_eval_combine
   // self-cleans after each eval; solves wipe the whole control block)
   // ONE fused kernel: Q@X + G, projection at X, and all three scalars
   // <P,P> / <QX+G,X> / <G,X> (the standalone <G,X> k_dots re-read
   // 2x the iterate from HBM and was the eval phase's fattest kernel
   // at 1M poses — profiles/r2c_narrow)
-  launch_hess_fused<0>(c->q_rp, c->q_ci, c->q_vals, X, X, c->Gt,
-                       c->grad, nullptr, c->ctrl, n, d, r,
-                       C_DOT1, C_DOT0, -1, s, c->Gt ? C_DOT2 : -1);
+  ctx_hess<0>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0, -1, s,
+              c->Gt ? C_DOT2 : -1);
   hipLaunchKernelGGL(k_eval_combine, dim3(1), dim3(64), 0, s, c->ctrl,
                      out_dev);
 }
@@ -2648,7 +2572,7 @@ static void enqueue_eval_body(DpoCtx* c, const double* X, const double* nbr,
 // fan-out path: one gather kernel waits on every agent's OUT fence).
 static void round_eval_impl(DpoCtx* c, const double* X, const double* nbr,
                             double* out_dev, hipStream_t s,
-                            bool wait_out) {
+                            bool wait_out = true) {
   static const bool no_graph = dpo_env_flag("DPO_NO_EVAL_GRAPH");
   if (no_graph) {
     enqueue_eval_body(c, X, nbr, out_dev, s);
@@ -2671,6 +2595,21 @@ void dpo_round_eval(void* h, const double* X, const double* nbr,
   hipStream_t s = (hipStream_t)stream;
   fence_signal(c, F_EVAL_IN, s);
   round_eval_impl(c, X, nbr, out_dev, s);
+}
+
+void dpo_round_eval_async(void* h, const double* X, const double* nbr,
+                          double* out_dev, void* join_stream) {
+  DpoCtx* c = (DpoCtx*)h;
+  hipStream_t js = (hipStream_t)join_stream;
+  // IN fence on the producer stream: carries the boundary-pose scatter
+  fence_signal(c, F_EVAL_IN, js);
+  round_eval_impl(c, X, nbr, out_dev, c->exec_stream, true);
+  DPO_CHECK(hipEventRecord(c->done_event, c->exec_stream));
+}
+
+void dpo_eval_join(void* h, void* join_stream) {
+  DpoCtx* c = (DpoCtx*)h;
+  DPO_CHECK(hipStreamWaitEvent((hipStream_t)join_stream, c->done_event, 0));
 }
 
 // --- multi-agent round fan-out --------------------------------------
@@ -3081,15 +3020,11 @@ __global__ void k_cert_norm(const double* __restrict__ w,
 static void launch_cert_lambda(const double* X, const double* QX,
                                double* lam, double* part, int n, int d,
                                int r, hipStream_t s) {
-#define CASE_CL(D, R) \
-  if (d == D && r == R) { \
-    hipLaunchKernelGGL((k_cert_lambda<D, R>), dim3(cert_grid(n)), \
-                       dim3(CERT_BS), 0, s, X, QX, lam, part, n); \
-    return; \
-  }
-  DPO_FOREACH_DR(CASE_CL)
-#undef CASE_CL
-  dpo_bad_shape(d, r);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_cert_lambda<Dc, Rc>), dim3(cert_grid(n)),
+                           dim3(CERT_BS), 0, s, X, QX, lam, part, n);
+      }))
+    dpo_bad_shape(d, r);
 }
 
 static void launch_cert_apply(const int* rp, const int* ci,

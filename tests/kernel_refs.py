@@ -575,10 +575,12 @@ def ctrl_tol(model: np.ndarray) -> np.ndarray:
 def model_solve(problem, X0: Tensor, tol: float, Delta0: float,
                 max_inner: int, accept_rho: float = 0.1,
                 max_shrink: int = 10, theta: float = 1.0,
-                kappa: float = 0.1):
+                kappa: float = 0.1, attempts: Optional[list] = None):
     """One RBCD local solve with the vector work in torch on the CPU and
     every scalar decision taken by CtrlModel, in the order the device
-    solve enqueues them. Returns (X, ctrl block, final status)."""
+    solve enqueues them. Returns (X, ctrl block, final status). A list
+    passed as `attempts` receives one record per candidate: radius,
+    use_current, jstar, rho, dm and the candidate point Xp."""
     assert max_inner <= MAX_TCG
     man = problem.manifold
     m = CtrlModel()
@@ -632,6 +634,12 @@ def model_solve(problem, X0: Tensor, tol: float, Delta0: float,
         c[C_DOT0] = float((problem.Q.spmm(Xp) * Xp).sum())
         c[C_DOT2] = float((G * Xp).sum())
         m.accept(accept_rho)
+        if attempts is not None:
+            attempts.append({
+                "radius": float(c[C_RADIUS]),
+                "use_current": c[C_USE_CURRENT] != 0.0,
+                "jstar": int(c[C_JSTAR]), "rho": float(c[C_RHO]),
+                "dm": float(c[C_DM]), "Xp": Xp})
         if c[C_STATUS] == ST_ACCEPTED:
             return Xp, c, ST_ACCEPTED
     return X0, c, ST_GIVE_UP
@@ -689,6 +697,44 @@ def solve_problem(d: int, r: int, with_g: bool = False):
     if with_g:
         p.set_g(randn(g, (d + 1) * n, r))
     return p, X
+
+
+# Device shrink loop: solves on solve_problem(d, r) that reject every
+# candidate (accept_rho = 2 is above any rho these problems produce), so
+# the whole batched loop runs and the last attempt's scalars reach the
+# host. (d, r, Delta0, max_shrink); tol = 1e-2, max_inner = 10.
+SHRINK_ACCEPT_RHO = 2.0
+SHRINK_CASES = (
+    (3, 8, 1e5, 3),     # attempts 0-2 full step, attempt 3 replays jstar = 1
+    (3, 5, 640.0, 1), (3, 5, 640.0, 2), (3, 5, 640.0, 3),
+    (2, 2, 640.0, 1), (2, 2, 640.0, 2), (2, 2, 640.0, 3),
+)
+
+
+def f_bound(problem, X: Tensor) -> float:
+    """Bound on the error of f(X) = 0.5 <QX, X> + <G, X> as the fused
+    Hessian kernel's dot slots give it (eval_terms_ref's rule)."""
+    return float(eval_terms_ref(problem, X)[1][0])
+
+
+_shrink_refs = {}
+
+
+def shrink_case_ref(d: int, r: int, Delta0: float, max_shrink: int):
+    """model_solve of one SHRINK_CASES entry, computed once: (problem, X0,
+    ctrl block, status, attempts, rho bound). rho = (fX - fprop) / dm: the
+    error of fX - fprop is at most the sum of the two f bounds (at X0 and
+    at the last candidate), and dm is the model's C_DM."""
+    key = (d, r, Delta0, max_shrink)
+    if key not in _shrink_refs:
+        p, X0 = solve_problem(d, r)
+        attempts = []
+        _, c, status = model_solve(p, X0, 1e-2, Delta0, 10,
+                                   accept_rho=SHRINK_ACCEPT_RHO,
+                                   max_shrink=max_shrink, attempts=attempts)
+        b_rho = (f_bound(p, X0) + f_bound(p, attempts[-1]["Xp"])) / c[C_DM]
+        _shrink_refs[key] = (p, X0, c, status, attempts, b_rho)
+    return _shrink_refs[key]
 
 
 def small_problem(d: int, r: int, n: int, g: torch.Generator,

@@ -504,6 +504,33 @@ def test_local_solve_matches_host(d, r):
         assert torch.allclose(Xd.cpu(), Xh, atol=1e-6, rtol=0), label
 
 
+@pytest.mark.parametrize("d,r,Delta0,max_shrink", kr.SHRINK_CASES)
+def test_shrink_loop_matches_model(d, r, Delta0, max_shrink):
+    """The batched device shrink loop against kr.model_solve on a solve
+    that rejects every candidate (accept_rho = 2): all max_shrink attempts
+    run, the host reads the last one. The status, the shrink count and
+    the history length are exact, X is untouched, and rho — which differs
+    from attempt to attempt by far more than its bound (checked on the
+    CPU in test_kernel_refs) — is the last attempt's."""
+    hb = _hb()
+    p, X, c, status, attempts, b_rho = kr.shrink_case_ref(d, r, Delta0,
+                                                          max_shrink)
+    assert status == kr.ST_GIVE_UP and len(attempts) == max_shrink + 1
+    ds = hb.DeviceSolver(p.n, d, r, DEV, max_inner=10)
+    Xd = _dev(X.clone())
+    st = ds.solve(_device_problem(p), Xd, tol=1e-2, Delta0=Delta0,
+                  max_shrink=max_shrink, accept_rho=kr.SHRINK_ACCEPT_RHO,
+                  compute_final_gradnorm=False)
+    label = f"shrink d={d} r={r} Delta0={Delta0:g} max_shrink={max_shrink}"
+    print(label, st, "hlen", ds._stats[7], "model rho", c[kr.C_RHO],
+          "|drho|", abs(st["rho"] - c[kr.C_RHO]), "bound", b_rho)
+    assert st["status"] == hb.ST_GIVE_UP, label
+    assert st["shrinks"] == max_shrink, label
+    assert ds._stats[7] == c[kr.C_HLEN], label
+    assert torch.equal(Xd.cpu(), X), label
+    assert abs(st["rho"] - c[kr.C_RHO]) <= b_rho, label
+
+
 def run_wide_child():
     """Body of the DPO_HESS_WIDE=1 child process: eval_terms and
     proj_dots through the element-per-thread kernels, each against the

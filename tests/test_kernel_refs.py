@@ -243,3 +243,40 @@ def test_boundary_tau_lands_on_the_radius():
     tau = c[kr.C_COEF]
     lhs = 1.5 + 2 * tau * 0.3 + tau * tau * 0.8
     assert abs(lhs - 4.0) <= 1e-12 * 4.0 and tau > 0
+
+
+@pytest.mark.parametrize("d,r,Delta0,max_shrink", kr.SHRINK_CASES)
+def test_shrink_cases_tell_the_attempts_apart(d, r, Delta0, max_shrink):
+    """What keeps the device shrink test honest: every case gives up
+    after exactly max_shrink shrinks, and the rho the host must read (the
+    last attempt's) is at least 100 rho bounds away from the rho of every
+    earlier attempt, so a replay that stopped early, skipped a shrink or
+    formed the step of another attempt cannot pass. Attempts that take
+    the same full step share one rho by construction (the (3, 8) case
+    has three); they are told apart from the last one, which is what the
+    device reports."""
+    p, X0, c, status, attempts, b_rho = kr.shrink_case_ref(d, r, Delta0,
+                                                           max_shrink)
+    assert status == kr.ST_GIVE_UP
+    assert c[kr.C_SHRINKS] == max_shrink == len(attempts) - 1
+    assert c[kr.C_RHO] == attempts[-1]["rho"] < kr.SHRINK_ACCEPT_RHO
+    assert c[kr.C_RADIUS] == Delta0 * 0.25 ** max_shrink
+    assert 0.0 < b_rho < 1e-6
+    for a in attempts[:-1]:
+        assert abs(a["rho"] - attempts[-1]["rho"]) >= 100.0 * b_rho
+    # successive attempts with different steps differ as clearly
+    for a, b in zip(attempts, attempts[1:]):
+        same_step = a["use_current"] and b["use_current"]
+        assert same_step or abs(a["rho"] - b["rho"]) >= 100.0 * b_rho
+
+
+def test_shrink_case_switches_from_full_step_to_replay():
+    """The (3, 8) case: the full step (C_USE_CURRENT = 1) survives three
+    radii, the fourth truncates the stored path at snapshot jstar = 1."""
+    _, _, c, _, attempts, _ = kr.shrink_case_ref(3, 8, 1e5, 3)
+    assert [a["use_current"] for a in attempts] == [True, True, True, False]
+    assert attempts[-1]["jstar"] == 1 and c[kr.C_JSTAR] == 1
+    assert c[kr.C_USE_CURRENT] == 0.0 and c[kr.C_HLEN] > 2
+    assert abs(attempts[0]["rho"] - 1.416412642) < 1e-8
+    assert abs(attempts[-1]["rho"] - 1.286575622) < 1e-8
+    assert attempts[-1]["radius"] == 1562.5
