@@ -97,6 +97,13 @@ class PGOAgent:
         self._nbr_slot_order: List[PoseID] = []
         self._manifold: Optional[LiftedSEManifold] = None
 
+        # SoA construction / packed GPU path (set_pose_graph_arrays,
+        # _ensure_packed, _packed_gnc_setup)
+        self._soa = False
+        self._dev_solver = None
+        self._packed_ready = False
+        self._gnc_ready = False
+
         self.YLift: Optional[np.ndarray] = None
         if agent_id == 0:
             self.YLift = lifting_matrix(self.d, self.r)
@@ -228,7 +235,7 @@ class PGOAgent:
                     print(f"agent {self.id}: missing neighbor pose {pid}")
                 return False
             buf[k] = v.T  # (r, dh) -> (dh, r)
-        if getattr(self, "_soa", False):
+        if self._soa:
             w = torch.from_numpy(self._shared_ma.weight.copy())
         else:
             w = torch.tensor([m.weight for m in self.shared_lc],
@@ -348,7 +355,7 @@ class PGOAgent:
     def has_shared_lc(self) -> bool:
         """True when this agent has inter-robot loop closures (works for
         both object-mode and SoA agents)."""
-        if getattr(self, "_soa", False):
+        if self._soa:
             return len(self._shared_ma) > 0
         return bool(self.shared_lc)
 
@@ -575,7 +582,7 @@ class PGOAgent:
                 and self.params.algorithm == OptAlgorithm.RTR):
             # Device-resident solve: tCG control state lives on the GPU,
             # one host sync per local solve.
-            if getattr(self, "_dev_solver", None) is None:
+            if self._dev_solver is None:
                 from .ops.hip_backend import DeviceSolver
                 self._dev_solver = DeviceSolver(self.n, self.d, self.r,
                                                 self.device, max_inner=10)
@@ -653,7 +660,7 @@ class PGOAgent:
 
     def update_loop_closures_weights(self) -> None:
         assert self.state == PGOAgentState.INITIALIZED
-        if getattr(self, "_soa", False):
+        if self._soa:
             raise RuntimeError(
                 "SoA agents update GNC weights via the packed GPU path "
                 "(_packed_update_weights); robust SoA needs a cuda device")
@@ -930,17 +937,17 @@ class PGOAgent:
         self.state = PGOAgentState.INITIALIZED
 
     def _weights_tensor(self) -> Tensor:
-        if getattr(self, "_soa", False):
+        if self._soa:
             return torch.from_numpy(self._all_ma.weight.copy())
         return torch.tensor([m.weight for m in self._all_meas],
                             dtype=torch.float64)
 
     # ------------------------------------------------------------------
     # packed fast path (GPU): device-tensor neighbor buffers + native
-    # C++ solve/eval, driven by DistributedRBCDDriver._run_packed.
+    # C++ solve/eval, driven by dpo_amd.packed.PackedBackend.
     # ------------------------------------------------------------------
     def _ensure_packed(self, dev) -> None:
-        if getattr(self, "_packed_ready", False):
+        if self._packed_ready:
             return
         n_slots = len(self._nbr_slot_order)
         self._nbr_buffer = torch.zeros(max(n_slots, 1), self.dh, self.r,
@@ -950,13 +957,13 @@ class PGOAgent:
         # private | shared); the shared tail doubles as the G-assembly
         # weight view and the exchange payload.
         self._all_weights_dev = self._weights_tensor().to(dev)
-        if getattr(self, "_soa", False):
+        if self._soa:
             nsh = len(self._shared_ma)
         else:
             nsh = len(self.shared_lc)
         self._shared_w_off = self._all_weights_dev.numel() - nsh
         self._w_shared_dev = self._all_weights_dev[self._shared_w_off:]
-        if getattr(self, "_dev_solver", None) is None:
+        if self._dev_solver is None:
             from .ops.hip_backend import DeviceSolver
             self._dev_solver = DeviceSolver(self.n, self.d, self.r, dev,
                                             max_inner=10)
@@ -974,22 +981,8 @@ class PGOAgent:
             self.alpha = 0.0
         self._packed_ready = True
 
-    def _packed_solve(self, accel: bool) -> None:
-        if accel:
-            self.X.copy_(self.Y)
-        nbr = self._nbr_buffer_aux if accel else self._nbr_buffer
-        for _ in range(self.params.tr_max_iterations):
-            self._dev_solver.round_solve(self.X, nbr,
-                                         tol=self.params.inner_tol,
-                                         Delta0=100.0)
-
-    def _packed_eval(self, out=None):
-        """Device 3-vector [f, 0.5<X,G>, ||rgrad||^2] with fresh G.
-        With an explicit out row the RAW enqueue is used so the whole
-        phase can be captured into one driver-level graph."""
-        if out is not None:
-            self._dev_solver.round_eval_raw(self.X, self._nbr_buffer, out)
-            return out
+    def _packed_eval(self):
+        """Device 3-vector [f, 0.5<X,G>, ||rgrad||^2] with fresh G."""
         return self._dev_solver.round_eval(self.X, self._nbr_buffer)
 
     def _packed_solve_async(self, accel: bool, first: bool = True) -> None:
@@ -1012,10 +1005,10 @@ class PGOAgent:
     # --- packed robust (GNC) support ----------------------------------
     def _packed_gnc_setup(self, dev) -> None:
         """Device tensors for the GNC weight-update kernel. SoA mode."""
-        if getattr(self, "_gnc_ready", False):
+        if self._gnc_ready:
             return
         from .measurements import concat_measurement_arrays
-        assert getattr(self, "_soa", False), \
+        assert self._soa, \
             "packed robust mode requires set_pose_graph_arrays"
         priv, sh = self._priv_ma, self._shared_ma
         n_odo = len(self._odo_ma)
@@ -1106,10 +1099,6 @@ class PGOAgent:
                       self._q_dev["edge_of"], self._all_weights_dev, self.dh)
         self.problem.refresh_preconditioner()
         self._dev_solver.bind_problem_static(self.problem)
-        self._packed_generation = getattr(self, "_packed_generation", 0) + 1
-
-    def _packed_shared_weights(self) -> Tensor:
-        return self._w_shared_dev
 
     def _packed_nesterov_pre(self) -> None:
         from .ops import hip_backend as hb

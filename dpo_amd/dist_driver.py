@@ -49,6 +49,75 @@ def _adjacency_from_ma(ma, num_poses):
     return [sorted(x) for x in nbr]
 
 
+class _PhaseClock:
+    """DPO_TIME_PHASES=1: host time spent in each phase call of a round
+    (perf_counter reads only; nothing is synchronized)."""
+
+    def __init__(self, on: bool):
+        self.on = on
+        self.t = dict.fromkeys(
+            ("solve_enq", "finish", "pack", "eval", "flush"), 0.0)
+
+    def __call__(self, phase: str, fn, *args):
+        if not self.on:
+            return fn(*args)
+        t = time.perf_counter()
+        out = fn(*args)
+        self.t[phase] += time.perf_counter() - t
+        return out
+
+
+class _DictBackend:
+    """Round mechanism over the agents' host-side neighbor dicts: runs
+    on CPU, over gloo, and with agents that are not yet initialized. The
+    operations mirror dpo_amd.packed.PackedBackend."""
+
+    time_phases = False
+
+    def __init__(self, drv: "DistributedRBCDDriver"):
+        self.drv = drv
+        self.sync_weights = (drv.robust != RobustCostType.L2
+                             and not drv._soa and drv._n_cross > 0)
+        self.active: List[int] = []
+
+    def eval_buffer(self, rounds: int) -> Tensor:
+        return torch.zeros(rounds, self.drv.num_robots, 3,
+                           dtype=torch.float64)
+
+    def begin(self) -> None:
+        """Round-0 pre-exchange so G terms exist before the first solve."""
+        self.exchange(0)
+
+    def reweight_due(self, round_counter: int) -> bool:
+        return False    # GNC runs inside PGOAgent.iterate on this path
+
+    def reweight(self) -> None:
+        pass
+
+    def select(self, active: List[int]) -> None:
+        self.active = active
+
+    def solve(self) -> None:
+        for rb, a in self.drv.local_agents.items():
+            a.iterate(rb in self.active)
+        if self.sync_weights:
+            self.drv._dict_sync_weights()
+
+    def exchange(self, it: int) -> None:
+        drv = self.drv
+        flats = drv.comm.all_gather_flat(drv._pack_rank_payload(),
+                                         drv.rank_sizes)
+        drv._unpack_and_update(flats)
+
+    def evaluate(self, row: Tensor) -> None:
+        row.zero_()
+        for rb, a in self.drv.local_agents.items():
+            row[rb] = torch.from_numpy(self.drv._eval_scalars(a))
+
+    def finish(self) -> None:
+        pass
+
+
 class DistributedRBCDDriver:
     def __init__(self,
                  measurements: Sequence[RelativeSEMeasurement],
@@ -277,6 +346,12 @@ class DistributedRBCDDriver:
             colors[rb] = c
         self._colors = colors
         self._num_colors = max(colors) + 1 if colors else 1
+        self._color_active = [
+            [rb for rb in range(num_robots) if colors[rb] == c]
+            for c in range(self._num_colors)]
+
+        self._packed = None      # PackedBackend, built by the first GPU run
+        self._round_counter = 0  # GNC cadence, counted across run() calls
 
     def _robust_is_l2(self) -> bool:
         return all(a.params.robust_cost_type == RobustCostType.L2
@@ -408,610 +483,142 @@ class DistributedRBCDDriver:
                 m.weight = float(wn[cm[k]])
             a.publish_weights_requested = False
 
-    def _evaluate(self) -> Tuple[float, np.ndarray]:
-        """Centralized cost + per-agent centralized block grad-norm^2,
-        from fresh neighbor data: one all-reduce of num_robots+1 fp64."""
-        vec = torch.zeros(self.num_robots + 1, dtype=torch.float64)
-        for rb, a in self.local_agents.items():
-            ev = self._eval_scalars(a)
-            vec[0] += ev[0] - ev[1]
-            vec[1 + rb] = ev[2]
-        self.comm.all_reduce_sum_(vec)
-        v = vec.numpy()
-        return float(v[0]), v[1:]
-
-    def run(self, max_iters: int = 1000, gradnorm_tol: float = 0.1,
-            trace_file: Optional[str] = None,
-            time_limit_s: Optional[float] = None) -> RBCDResult:
-        import torch
+    # -------------------------------------------------------------------
+    # The round loop. Policy lives here; the mechanism of a round is a
+    # backend: _DictBackend below (host dicts; CPU, gloo, uninitialized
+    # agents) or dpo_amd.packed.PackedBackend (device tensors end to end).
+    # -------------------------------------------------------------------
+    def _backend(self):
         if (str(self.device).startswith("cuda")
                 and (self._robust_is_l2() or self._soa)
                 and all(a.state == PGOAgentState.INITIALIZED
                         for a in self.local_agents.values())):
-            return self._run_packed(max_iters, gradnorm_tol, trace_file,
-                                    time_limit_s)
+            if self._packed is None:
+                from .packed import PackedBackend
+                self._packed = PackedBackend(self)
+            return self._packed
+        return _DictBackend(self)
+
+    def _readback_chunk(self, gradnorm_tol: float) -> int:
+        """Rounds between readbacks of the eval scalars. Evaluations land
+        in a ring and are read every `chunk` rounds, so a device backend
+        overlaps the eval of round t with the solves of round t+1 instead
+        of draining at a host sync every round. tol <= 0 and no argmax
+        selection: nothing to decide per round -> deep ring. colored with
+        tol > 0: the stop test runs on ring flushes — the crossing
+        iteration is read exactly from the per-round entries, only the
+        break comes up to chunk-1 (monotone) rounds later. Every other
+        case decides on the host each round."""
+        if gradnorm_tol <= 0.0 and self.selection not in (
+                "greedy", "colored_greedy"):
+            return 16
+        if self.selection == "colored":
+            return 8
+        return 1
+
+    def _active_set(self, it: int, selected: int) -> List[int]:
+        if self.selection == "colored":
+            return self._color_active[it % self._num_colors]
+        if self.selection == "colored_greedy":
+            # the whole independent set (color) that contains the
+            # max-gradient agent: greedy's targeting with colored's
+            # concurrent block updates
+            return self._color_active[self._colors[selected]]
+        if self.selection == "round_robin":
+            return [it % self.num_robots]
+        return [selected]
+
+    def run(self, max_iters: int = 1000, gradnorm_tol: float = 0.1,
+            trace_file: Optional[str] = None,
+            time_limit_s: Optional[float] = None) -> RBCDResult:
+        backend = self._backend()
+        clock = _PhaseClock(backend.time_phases)
         res = RBCDResult()
-        selected = 0
         t0 = time.perf_counter()
-        # round 0 pre-exchange so G terms exist before the first solve
-        flats = self.comm.all_gather_flat(self._pack_rank_payload(),
-                                          self.rank_sizes)
-        self._unpack_and_update(flats)
-        del flats
+        chunk = self._readback_chunk(gradnorm_tol)
+        # (rounds, num_robots, 3) rows of [f, 0.5<X,G>, ||rgrad||^2]
+        first = backend.eval_buffer(1)
+        ring = first if chunk == 1 else backend.eval_buffer(chunk)
+        backend.begin()
         fout = open(trace_file, "w") if (trace_file and
                                          self.comm.rank == 0) else None
+        queued: List[Tuple[int, List[int]]] = []  # evaluated, not read back
+
+        def flush() -> Optional[int]:
+            """Read the queued rounds back (the host sync), record them,
+            and return the last round's max-gradient agent."""
+            if not queued:
+                return None
+            slab = ring[:len(queued)]
+            self.comm.all_reduce_sum_(slab)
+            ev = slab.cpu().numpy()
+            for (it, active), row in zip(queued, ev):
+                cost = 2.0 * float((row[:, 0] - row[:, 1]).sum())
+                gradnorm = float(np.sqrt(row[:, 2].sum()))
+                res.trace.append((cost, gradnorm))
+                if fout:
+                    fout.write(f"{cost:.10g},{gradnorm:.10g}\n")
+                if self.verbose and self.comm.rank == 0:
+                    print(f"iter {it} active {active} cost {cost:.5g} "
+                          f"gn {gradnorm:.5g}")
+            top = int(np.argmax(ev[-1, :, 2]))
+            if chunk > 1:
+                slab.zero_()
+            queued.clear()
+            return top
+
         # the reference checks convergence BEFORE the first iteration
         # (MultiRobotExample.cpp:302-305): an already-converged start
         # reports 0 iterations (e.g. kitti_08)
         if gradnorm_tol > 0.0:
-            cost0, gn20 = self._evaluate()
-            gradnorm0 = float(np.sqrt(gn20.sum()))
-            if gradnorm0 < gradnorm_tol:
-                res.converged = True
-                res.final_cost = 2.0 * cost0
-                res.final_gradnorm = gradnorm0
-                if fout:
-                    fout.close()
-                res.elapsed_s = time.perf_counter() - t0
-                return res
-        for it in range(max_iters):
-            if self.selection == "colored":
-                color = it % self._num_colors
-                active = [rb for rb in range(self.num_robots)
-                          if self._colors[rb] == color]
-            elif self.selection == "colored_greedy":
-                # activate the whole independent set (color) that
-                # contains the max-gradient agent: greedy's targeting
-                # with colored's concurrent block updates
-                color = self._colors[selected]
-                active = [rb for rb in range(self.num_robots)
-                          if self._colors[rb] == color]
-            elif self.selection == "round_robin":
-                active = [it % self.num_robots]
-            else:
-                active = [selected]
-            for rb, a in self.local_agents.items():
-                a.iterate(rb in active)
-            if self.robust != RobustCostType.L2 and not self._soa \
-                    and self._n_cross:
-                self._dict_sync_weights()
-            flats = self.comm.all_gather_flat(self._pack_rank_payload(),
-                                              self.rank_sizes)
-            self._unpack_and_update(flats)
-            cost, gn2 = self._evaluate()
-            gradnorm = float(np.sqrt(gn2.sum()))
-            res.trace.append((2.0 * cost, gradnorm))
-            if fout:
-                fout.write(f"{2.0 * cost:.10g},{gradnorm:.10g}\n")
-            if self.verbose and self.comm.rank == 0:
-                print(f"iter {it} active {active} cost {2 * cost:.5g} "
-                      f"gn {gradnorm:.5g}")
-            res.iterations = it + 1
-            if gradnorm < gradnorm_tol:
-                res.converged = True
-                break
-            if time_limit_s and time.perf_counter() - t0 > time_limit_s:
-                break
-            if self.selection != "round_robin":
-                selected = int(np.argmax(gn2))
-        if res.trace:
-            res.final_cost, res.final_gradnorm = res.trace[-1]
-        if fout:
-            fout.close()
-        res.elapsed_s = time.perf_counter() - t0
-        return res
-
-    # ===================================================================
-    # Packed fast path (GPU, L2 cost, all agents initialized):
-    # device-tensor payloads end-to-end, native C++ solve + eval, one
-    # host sync per round. Used automatically by run() when applicable.
-    # ===================================================================
-    def _packed_setup(self):
-        if getattr(self, "_pk", None) is not None:
-            return
-        import torch
-        dev = torch.device(self.device)
-        blk = self.dh * self.r
-        pk = {}
-        pk["rank_payload_len"] = [
-            sum(len(self.pub_idx[rb]) * blk for rb in agents)
-            for agents in self.rank_agents]
-        # global offsets: agent rb's block inside its owner's payload
-        glob_off = {}
-        for rk, agents in enumerate(self.rank_agents):
-            o = 0
-            for rb in agents:
-                glob_off[rb] = o
-                o += len(self.pub_idx[rb]) * blk
-        pk["glob_off"] = glob_off
-
-        # ---- consolidated per-rank buffers --------------------------
-        # One X buffer and one neighbor buffer for all local agents:
-        # pack/scatter become single index ops, and each agent's tensors
-        # are stable contiguous views (the hipGraph keys stay valid).
-        my = self.rank_agents[self.comm.rank]
-        for rb in my:
-            self.local_agents[rb]._ensure_packed(dev)
-        pose_off = {}
-        off = 0
-        for rb in my:
-            pose_off[rb] = off
-            off += self.local_agents[rb].n
-        rank_X = torch.zeros(off * self.dh, self.r, dtype=torch.float64,
-                             device=dev)
-        for rb in my:
-            a = self.local_agents[rb]
-            o = pose_off[rb] * self.dh
-            rank_X[o:o + a.n * self.dh].copy_(a.X)
-            a.X = rank_X[o:o + a.n * self.dh]
-            if a.params.acceleration:
-                a.Y = a.X.clone()
-                a.V = a.X.clone()
-        pk["rank_X"] = rank_X
-        slot_off = {}
-        soff = 0
-        for rb in my:
-            slot_off[rb] = soff
-            soff += max(len(self.local_agents[rb]._nbr_slot_order), 1)
-        rank_nbr = torch.zeros(max(soff, 1), self.dh, self.r,
-                               dtype=torch.float64, device=dev)
-        rank_nbr_aux = torch.zeros_like(rank_nbr)
-        for rb in my:
-            a = self.local_agents[rb]
-            ns = max(len(a._nbr_slot_order), 1)
-            a._nbr_buffer = rank_nbr[slot_off[rb]:slot_off[rb] + ns]
-            a._nbr_buffer_aux = rank_nbr_aux[slot_off[rb]:slot_off[rb] + ns]
-        pk["rank_nbr"] = rank_nbr
-        pk["rank_nbr_aux"] = rank_nbr_aux
-
-        # single pack index: global pose-block rows of every public pose
-        pack_rows = []
-        for rb in my:
-            for p in self.pub_idx[rb]:
-                pack_rows.append(pose_off[rb] + p)
-        pk["pack_rows"] = torch.tensor(pack_rows, dtype=torch.int64,
-                                       device=dev)
-        # scatter: one (src positions -> nbr slots) pair per SOURCE rank
-        pub_payload_pos = {}  # (nb agent, pose) -> index in owner payload
-        for rb in range(self.num_robots):
-            base = glob_off[rb] // blk
-            for k, p in enumerate(self.pub_idx[rb]):
-                pub_payload_pos[(rb, p)] = base + k
-        per_src = {}
-        for rb in my:
-            a = self.local_agents[rb]
-            for slot, (nb, p) in enumerate(a._nbr_slot_order):
-                rk = self.owner[nb]
-                per_src.setdefault(rk, ([], []))
-                per_src[rk][0].append(pub_payload_pos[(nb, p)])
-                per_src[rk][1].append(slot_off[rb] + slot)
-        pk["scatter_rank"] = {
-            rk: (torch.tensor(src, dtype=torch.int64, device=dev),
-                 torch.tensor(dst, dtype=torch.int64, device=dev))
-            for rk, (src, dst) in per_src.items()}
-        pk["dev"] = dev
-        self._pk = pk
-
-    def _packed_pack(self, use_aux: bool = False):
-        import torch
-        pk = self._pk
-        if not self.rank_agents[self.comm.rank]:
-            return torch.zeros(0, dtype=torch.float64, device=pk["dev"])
-        if use_aux:
-            parts = []
-            for rb in self.rank_agents[self.comm.rank]:
-                a = self.local_agents[rb]
-                src = a.Y if a.Y is not None else a.X
-                n_pub = len(self.pub_idx[rb])
-                Xb = src.view(a.n, self.dh, self.r)
-                idx = torch.tensor(self.pub_idx[rb], dtype=torch.int64,
-                                   device=pk["dev"])
-                parts.append(Xb.index_select(0, idx).reshape(-1))
-            return torch.cat(parts) if parts else torch.zeros(
-                0, dtype=torch.float64, device=pk["dev"])
-        Xb = pk["rank_X"].view(-1, self.dh, self.r)
-        return Xb.index_select(0, pk["pack_rows"]).reshape(-1)
-
-    def _packed_scatter(self, flats, aux: bool = False):
-        pk = self._pk
-        blk = self.dh * self.r
-        target = pk["rank_nbr_aux"] if aux else pk["rank_nbr"]
-        for rk, (src_idx, dst_slots) in pk["scatter_rank"].items():
-            blkv = flats[rk].view(-1, self.dh, self.r)
-            target.index_copy_(0, dst_slots, blkv.index_select(0, src_idx))
-
-    def _packed_exchange_xy(self, sizes):
-        """Accelerated mode: ONE all-gather carries both the X public
-        poses and the Nesterov aux poses Y ([X | Y] halves per rank),
-        instead of two collectives per round (round-1 VERDICT item 9).
-        Callers must have run _packed_nesterov_pre so Y is current."""
-        import torch
-        payload = torch.cat([self._packed_pack(),
-                             self._packed_pack(use_aux=True)])
-        sizes2 = [2 * s for s in sizes]
-        flats = self.comm.all_gather_flat(payload, sizes2)
-        self._packed_scatter([f[:s] for f, s in zip(flats, sizes)])
-        self._packed_scatter([f[s:] for f, s in zip(flats, sizes)],
-                             aux=True)
-
-    def _packed_eval_phase(self, evalmat):
-        """Per-round evaluation of every local agent. The whole phase
-        (zeroing + every agent's G assembly + cost/gradient kernels,
-        writing directly into evalmat rows) is captured once into a
-        single hipGraph via torch.cuda.graph and replayed per round;
-        re-captured when an agent's problem pointers change (GNC Q
-        rebuild)."""
-        import torch
-        modes = getattr(self, "_eval_env_modes", None)
-        if modes is None:
-            # env decisions are fixed per driver (read once, not per round)
-            import os as _os
-            _sync_eval_default = ("0" if self.selection in (
-                "colored", "colored_greedy") else "1")
-            modes = self._eval_env_modes = (
-                _os.environ.get("DPO_DRIVER_EVAL_GRAPH", "0") == "1",
-                _os.environ.get("DPO_SYNC_EVAL", _sync_eval_default) == "1")
-        driver_graph, sync_eval = modes
-        gen = sum(getattr(a, "_packed_generation", 0)
-                  for a in self.local_agents.values())
-        cache = getattr(self, "_eval_graph", None)
-        if not driver_graph:
-            # Default: per-agent hip-captured eval graphs (or the colored
-            # schedule's per-stream fan-out). A single driver-level
-            # torch-captured graph over all agents measured ~20% faster
-            # but perturbs the evaluation run-to-run at the 1e-15 level,
-            # which the greedy selection chaotically amplifies into
-            # iteration-count scatter — parity with the reference's
-            # deterministic trajectories wins. Opt in with
-            # DPO_DRIVER_EVAL_GRAPH=1.
-            if sync_eval:
-                evalmat.zero_()
-                for rb, a in self.local_agents.items():
-                    a._packed_eval(out=None)
-                    evalmat[rb] = a._dev_solver._eval_out
-            elif getattr(self, "_group", None) is not None:
-                # native fan-out: one C call + one gather kernel
-                if not self._group_all:
-                    evalmat.zero_()
-                self._group.eval_all(evalmat)
-            else:
-                evalmat.zero_()
-                for rb, a in self.local_agents.items():
-                    a._packed_eval_async()
-                for rb, a in self.local_agents.items():
-                    evalmat[rb] = a._packed_eval_join()
-            return
-        # ROCm 7.2: a long-lived graph exec intermittently degrades after
-        # a few hundred replays (stale node state; fresh capture of the
-        # identical sequence is correct). Re-capture periodically —
-        # amortized cost ~1%.
-        if cache is not None and cache[2] >= 128:
-            cache = None
-        if cache is None or cache[1] != gen:
-            g = torch.cuda.CUDAGraph()
-            # warmup on a side stream (required before capture)
-            side = torch.cuda.Stream()
-            with torch.cuda.stream(side):
-                evalmat.zero_()
-                for rb, a in self.local_agents.items():
-                    a._packed_eval(out=evalmat[rb])
-            torch.cuda.current_stream().wait_stream(side)
-            with torch.cuda.graph(g):
-                evalmat.zero_()
-                for rb, a in self.local_agents.items():
-                    a._packed_eval(out=evalmat[rb])
-            self._eval_graph = [g, gen, 0]
-            cache = self._eval_graph
-        cache[0].replay()
-        cache[2] += 1
-
-    def _run_packed(self, max_iters, gradnorm_tol, trace_file, time_limit_s):
-        import torch
-        res = RBCDResult()
-        self._packed_setup()
-        pk = self._pk
-        dev = pk["dev"]
-        selected = 0
-        t0 = time.perf_counter()
-        # persistent eval buffers: stable pointers keep the native
-        # gather/eval graph caches hot across repeated run() calls
-        # (bench episodes)
-        if getattr(self, "_evalmat", None) is None \
-                or self._evalmat.device != dev:
-            self._evalmat = torch.zeros(self.num_robots, 3,
-                                        dtype=torch.float64, device=dev)
-        evalmat = self._evalmat
-        evalmat.zero_()
-        sizes = pk["rank_payload_len"]
-        accel = self.acceleration
-        # Nesterov host-side scalars per agent
-        if accel:
-            for a in self.local_agents.values():
-                a.gamma = 0.0
-                a.alpha = 0.0
-            # round-0 pre-exchange carries X and the first Y in one
-            # collective; per-round exchanges then stay single too
-            for a in self.local_agents.values():
-                a._packed_nesterov_pre()
-            self._packed_exchange_xy(sizes)
-        else:
-            flats = self.comm.all_gather_flat(self._packed_pack(), sizes)
-            self._packed_scatter(flats)
-        fout = open(trace_file, "w") if (trace_file and
-                                         self.comm.rank == 0) else None
-        robust_mode = not self._robust_is_l2()
-        if robust_mode:
-            for a in self.local_agents.values():
-                a._packed_gnc_setup(dev)
-            self._w_exch = torch.zeros(self._n_cross, dtype=torch.float64,
-                                       device=dev)
-            self._cross_map_t = {
-                rb: torch.from_numpy(self._cross_map[rb]).to(dev)
-                for rb in self.local_agents}
-            self._cross_owned_t = {
-                rb: torch.from_numpy(
-                    np.nonzero(self._cross_owned[rb])[0]).to(dev)
-                for rb in self.local_agents}
-        if not hasattr(self, "_round_counter"):
-            self._round_counter = 0
-        inner = next(iter(self.local_agents.values())).params \
-            .robust_opt_inner_iters if self.local_agents else 30
-        # reference semantics: convergence is checked BEFORE the first
-        # iteration (an already-converged start reports 0 iterations)
-        if gradnorm_tol > 0.0:
-            self._packed_eval_phase(evalmat)
-            self.comm.all_reduce_sum_(evalmat)
-            ev0 = evalmat.cpu().numpy()
+            backend.evaluate(first[0])
+            self.comm.all_reduce_sum_(first)
+            ev0 = first.cpu().numpy()[0]
             gradnorm0 = float(np.sqrt(ev0[:, 2].sum()))
             if gradnorm0 < gradnorm_tol:
                 res.converged = True
                 res.final_cost = 2.0 * float((ev0[:, 0] - ev0[:, 1]).sum())
                 res.final_gradnorm = gradnorm0
-                if fout:
-                    fout.close()
-                res.elapsed_s = time.perf_counter() - t0
-                self._sync_anchor()
-                return res
-        # Pipelined evaluation readback: when no per-round host decision
-        # is needed (no greedy selection, no gradient-norm stop test),
-        # the per-round eval scalars land in a device-side ring and are
-        # read back every `chunk` rounds — the eval kernels of round t
-        # then overlap the solves of round t+1 instead of draining the
-        # GPU at a .cpu() sync every round.
-        import os as _os_
-        _sync_solve = _os_.environ.get("DPO_SYNC_SOLVE", "0") == "1"
-        _timing = _os_.environ.get("DPO_TIME_PHASES", "0") == "1"
-        ph = [0.0] * 5  # solve-enqueue, solve-finish, pack+scatter,
-        #                 eval-enqueue, ring-flush
-        # native multi-agent fan-out (one C call per phase, fixed
-        # pointers keep the per-agent hipGraph caches hot)
-        if (str(dev).startswith("cuda") and self.local_agents
-                and getattr(self, "_group", None) is None
-                and _os_.environ.get("DPO_NO_GROUP", "0") != "1"):
-            from .ops.hip_backend import DeviceGroup
-            rbs = sorted(self.local_agents)
-            self._group = DeviceGroup(
-                [self.local_agents[rb]._dev_solver for rb in rbs],
-                [self.local_agents[rb].X for rb in rbs],
-                [self.local_agents[rb]._nbr_buffer for rb in rbs],
-                rbs)
-            self._group_lidx = {rb: i for i, rb in enumerate(rbs)}
-            self._group_all = len(rbs) == self.num_robots
-        group = getattr(self, "_group", None)
-        use_group_solve = (group is not None and not accel
-                           and not _sync_solve)
-        inner_tol = next(iter(self.local_agents.values())) \
-            .params.inner_tol if self.local_agents else 1e-2
-        tr_steps = next(iter(self.local_agents.values())) \
-            .params.tr_max_iterations if self.local_agents else 1
-        if self.selection in ("colored", "colored_greedy"):
-            color_active = [
-                [rb for rb in range(self.num_robots)
-                 if self._colors[rb] == c]
-                for c in range(self._num_colors)]
-            if group is not None:
-                color_ids = [
-                    group.ids([self._group_lidx[rb] for rb in ca
-                               if rb in self.local_agents])
-                    for ca in color_active]
-        # Pipelined eval readback width. tol<=0: nothing to decide per
-        # round -> deep ring. tol>0 with a selection that needs no
-        # per-round argmax (colored): still pipeline, checking the
-        # convergence test on ring flushes — the crossing ITERATION is
-        # read exactly from the per-round ring entries, only the break
-        # happens up to chunk-1 rounds later (extra monotone rounds).
-        if _os_.environ.get("DPO_DRIVER_EVAL_GRAPH", "0") == "1":
-            chunk = 1
-        elif gradnorm_tol <= 0.0 and self.selection not in (
-                "greedy", "colored_greedy"):
-            chunk = 16
-        elif self.selection == "colored":
-            chunk = 8
-        else:
-            chunk = 1
-        if chunk > 1:
-            er = getattr(self, "_evalring", None)
-            if er is None or er.shape[0] != chunk:
-                self._evalring = torch.zeros(chunk, self.num_robots, 3,
-                                             dtype=torch.float64,
-                                             device=dev)
-            evalring = self._evalring
-            evalring.zero_()
-        else:
-            evalring = None
-        pending = 0   # rounds evaluated but not yet read back
-
-        def flush_ring():
-            nonlocal pending
-            if pending == 0:
-                return
-            slab = evalring[:pending]
-            self.comm.all_reduce_sum_(slab)
-            evh = slab.cpu().numpy()
-            for k in range(pending):
-                c_ = float((evh[k, :, 0] - evh[k, :, 1]).sum())
-                g_ = float(np.sqrt(evh[k, :, 2].sum()))
-                res.trace.append((2.0 * c_, g_))
-                if fout:
-                    fout.write(f"{2.0 * c_:.10g},{g_:.10g}\n")
-            slab.zero_()
-            pending = 0
-
+                max_iters = 0   # no rounds: straight to the common exit
+        selected = 0
         for it in range(max_iters):
             self._round_counter += 1
-            if chunk > 1 and robust_mode \
-                    and self._round_counter % inner == 0:
-                flush_ring()
-            if robust_mode and self._round_counter % inner == 0:
-                # GNC re-weighting round (reference iterate():
-                # shouldUpdateLoopClosureWeights -> update -> mu step)
-                for rb, a in self.local_agents.items():
-                    a._packed_update_weights()
-                self._w_exch.zero_()
-                for rb, a in self.local_agents.items():
-                    own = self._cross_owned_t[rb]
-                    if own.numel():
-                        pos = self._cross_map_t[rb].index_select(0, own)
-                        self._w_exch.index_copy_(
-                            0, pos, a._w_shared_dev.index_select(0, own))
-                self.comm.all_reduce_sum_(self._w_exch)
-                for rb, a in self.local_agents.items():
-                    if self._cross_map_t[rb].numel():
-                        a._w_shared_dev.copy_(
-                            self._w_exch.index_select(
-                                0, self._cross_map_t[rb]))
-                for rb, a in self.local_agents.items():
-                    a._packed_rebuild_q()
-                    a.robust_cost.update()
-            if self.selection == "colored":
-                active = color_active[it % self._num_colors]
-            elif self.selection == "colored_greedy":
-                active = color_active[self._colors[selected]]
-            elif self.selection == "round_robin":
-                selected = it % self.num_robots
-                active = [selected]
-            else:
-                active = [selected]
-            # (accelerated mode: Y for this round was computed and
-            # exchanged together with X at the end of the previous round
-            # — the reference pulls aux dicts right before the selected
-            # iterate, MultiRobotExample.cpp:259-273, and nothing updates
-            # X/V between our round-end pre() and this solve, so the
-            # values are identical with half the collectives.)
-            # Concurrent active agents' solves overlap on per-agent HIP
-            # streams (data-flow fences in dpo_ops.hip order the cached
-            # solve/eval graphs against this stream's pack/scatter; the
-            # async path is bitwise-deterministic).
-            if _timing:
-                tA = time.perf_counter()
-            if use_group_solve:
-                if self.selection == "colored":
-                    gids = color_ids[it % self._num_colors]
-                elif self.selection == "colored_greedy":
-                    gids = color_ids[self._colors[selected]]
-                elif selected in self.local_agents:
-                    gids = group.ids([self._group_lidx[selected]])
-                else:
-                    gids = group.ids([])
-                if _timing:
-                    tB = time.perf_counter()
-                if len(gids):
-                    for _k in range(tr_steps):
-                        group.solve_start(gids, tol=inner_tol)
-                        group.solve_finish(gids)
-            else:
-                for rb, a in self.local_agents.items():
-                    if accel and rb not in active:
-                        a.X.copy_(a.Y)
-                if _timing:
-                    tB = time.perf_counter()
-                if _sync_solve:
-                    for rb, a in self.local_agents.items():
-                        if rb in active:
-                            a._packed_solve(accel)  # loops tr steps
-                else:
-                    for _k in range(tr_steps):
-                        for rb in active:
-                            if rb in self.local_agents:
-                                self.local_agents[rb]._packed_solve_async(
-                                    accel, first=(_k == 0))
-                        for rb in active:
-                            if rb in self.local_agents:
-                                self.local_agents[rb]._packed_solve_finish()
-            if _timing:
-                tC = time.perf_counter()
-            if accel:
-                for a in self.local_agents.values():
-                    a._packed_nesterov_post(it)
-                for a in self.local_agents.values():
-                    a._packed_nesterov_pre()
-                self._packed_exchange_xy(sizes)
-            else:
-                flats = self.comm.all_gather_flat(self._packed_pack(),
-                                                  sizes)
-                self._packed_scatter(flats)
-            if _timing:
-                tD = time.perf_counter()
-                ph[0] += tB - tA
-                ph[1] += tC - tB
-                ph[2] += tD - tC
-            # evaluation (fresh neighbor data); agents fan out on their
-            # own streams and join back before the packed reduce
-            if chunk > 1:
-                self._packed_eval_phase(evalring[pending])
-                pending += 1
-                res.iterations = it + 1
-                if _timing:
-                    ph[3] += time.perf_counter() - tD
-                if pending == chunk or it + 1 == max_iters:
-                    tE = time.perf_counter()
-                    scan_from = len(res.trace)
-                    flush_ring()
-                    if _timing:
-                        ph[4] += time.perf_counter() - tE
-                    if gradnorm_tol > 0.0:
-                        for k in range(scan_from, len(res.trace)):
-                            if res.trace[k][1] < gradnorm_tol:
-                                res.converged = True
-                                res.iterations = k + 1
-                                res.trace = res.trace[:k + 1]
-                                break
-                        if res.converged:
-                            break
-                    if time_limit_s and \
-                            time.perf_counter() - t0 > time_limit_s:
-                        break
-                continue
-            self._packed_eval_phase(evalmat)
-            self.comm.all_reduce_sum_(evalmat)
-            ev = evalmat.cpu().numpy()          # the round's one host sync
-            cost = float((ev[:, 0] - ev[:, 1]).sum())
-            gn2 = ev[:, 2]
-            gradnorm = float(np.sqrt(gn2.sum()))
-            res.trace.append((2.0 * cost, gradnorm))
-            if fout:
-                fout.write(f"{2.0 * cost:.10g},{gradnorm:.10g}\n")
+            if backend.reweight_due(self._round_counter):
+                # weights change the cost: read back what was evaluated
+                # under the old ones first (recorded, not stop-tested)
+                flush()
+                backend.reweight()
+            active = self._active_set(it, selected)
+            clock("solve_enq", backend.select, active)
+            clock("finish", backend.solve)
+            clock("pack", backend.exchange, it)
+            clock("eval", backend.evaluate, ring[len(queued)])
+            queued.append((it, active))
             res.iterations = it + 1
-            if gradnorm < gradnorm_tol:
+            if len(queued) < chunk and it + 1 < max_iters:
+                continue
+            scanned = len(res.trace)
+            selected = clock("flush", flush)
+            hit = next((k for k in range(scanned, len(res.trace))
+                        if res.trace[k][1] < gradnorm_tol), None)
+            if hit is not None:
+                # rounds run past the crossing are dropped from the result
                 res.converged = True
+                res.iterations = hit + 1
+                del res.trace[hit + 1:]
                 break
             if time_limit_s and time.perf_counter() - t0 > time_limit_s:
                 break
-            if self.selection != "round_robin":
-                selected = int(np.argmax(gn2))
-        if chunk > 1:
-            flush_ring()   # safety net: all exits above should have flushed
-        if _timing and self.comm.rank == 0 and res.iterations:
-            k = res.iterations
+        if clock.on and self.comm.rank == 0 and res.iterations:
             print("phase ms/round: solve_enq %.3f finish %.3f pack %.3f "
-                  "eval %.3f flush %.3f" % tuple(p / k * 1e3 for p in ph))
+                  "eval %.3f flush %.3f" % tuple(
+                      t / res.iterations * 1e3 for t in clock.t.values()))
         if res.trace:
             res.final_cost, res.final_gradnorm = res.trace[-1]
         if fout:
             fout.close()
         res.elapsed_s = time.perf_counter() - t0
-        # sync dict-path state (global anchor for rounding)
-        self._sync_anchor()
+        backend.finish()
         return res
 
     def snapshot_initial_state(self) -> None:
@@ -1039,7 +646,6 @@ class DistributedRBCDDriver:
         """Rounded global trajectory (d, (d+1) n) on rank 0 (reference
         PartitionInitial.cpp:329-335 output). Returns None on other
         ranks."""
-        import torch
         self._sync_anchor()
         dh = self.dh
         buf = torch.zeros(self.n_global, self.d, dh, dtype=torch.float64)
@@ -1063,7 +669,6 @@ class DistributedRBCDDriver:
         blocks in the `pose_to_index` order — the unrounded input of
         `dpo_amd.certify.certify_solution`. Returns None on other
         ranks."""
-        import torch
         dh = self.dh
         buf = torch.zeros(self.n_global, dh, self.r, dtype=torch.float64)
         for rb, a in self.local_agents.items():
@@ -1077,9 +682,8 @@ class DistributedRBCDDriver:
         return buf.view(self.n_global * dh, self.r)
 
     def _sync_anchor(self):
-        import torch
         blk = self.dh * self.r
-        dev = self._pk["dev"] if getattr(self, "_pk", None) else "cpu"
+        dev = self._packed.dev if self._packed is not None else "cpu"
         buf = torch.zeros(blk, dtype=torch.float64, device=dev)
         if 0 in self.local_agents:
             a0 = self.local_agents[0]

@@ -40,8 +40,7 @@ _lib.dpo_tcg_delta.argtypes = [_c, _c, _c, _l, _c]
 _lib.dpo_form_step.argtypes = [_c, _c, _c, _c, _c, _l, _c]
 _lib.dpo_axpby.argtypes = [_c, _c, _d, _d, _c, _l, _c]
 _lib.dpo_dots.argtypes = [_c, _c, _c, _c, _i, _i, _l, _i, _c]
-for name in ("dpo_ctrl_init",):
-    _lib.dpo_ctrl_init.argtypes = [_c, _d, _d, _d, _d, _c]
+_lib.dpo_ctrl_init.argtypes = [_c, _d, _d, _d, _d, _c]
 for name in ("dpo_ctrl_z0", "dpo_ctrl_alpha", "dpo_ctrl_rr", "dpo_ctrl_beta",
              "dpo_ctrl_tcg_end", "dpo_ctrl_candidate", "dpo_ctrl_shrink"):
     getattr(_lib, name).argtypes = [_c, _c]
@@ -62,7 +61,6 @@ _lib.dpo_round_solve.restype = _i
 _lib.dpo_round_solve.argtypes = [_c, _c, _c, _d, _d, _i, _d,
                                  ctypes.POINTER(ctypes.c_double), _c]
 _lib.dpo_round_eval.argtypes = [_c, _c, _c, _c, _c]
-_lib.dpo_round_eval_raw.argtypes = [_c, _c, _c, _c, _c]
 _lib.dpo_round_solve_async.argtypes = [_c, _c, _c, _d, _d, _d, _c]
 _lib.dpo_round_solve_finish.restype = _i
 _lib.dpo_round_solve_finish.argtypes = [
@@ -473,10 +471,6 @@ class DeviceSolver:
         return _lib.dpo_round_solve(self.handle, _p(X), _p(nbr), tol,
                                     Delta0, 10, 0.1, self._stats,
                                     _stream(X))
-
-    def round_eval_raw(self, X: Tensor, nbr: Tensor, out: Tensor) -> None:
-        _lib.dpo_round_eval_raw(self.handle, _p(X), _p(nbr), _p(out),
-                                _stream(X))
 
     def round_eval(self, X: Tensor, nbr: Tensor,
                    out: Optional[Tensor] = None) -> Tensor:

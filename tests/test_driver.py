@@ -298,3 +298,126 @@ def test_colored_greedy_selection_converges():
                                 selection="colored_greedy")
     res = drv.run(max_iters=400)
     assert res.converged
+
+
+# ---------------------------------------------------------------------
+# DistributedRBCDDriver round loop: golden traces and the readback ring
+# ---------------------------------------------------------------------
+def _ring_fixture_driver(selection="colored", acceleration=False):
+    from dpo_amd.comm import Comm
+    from dpo_amd.dist_driver import DistributedRBCDDriver
+    meas, n = grid3d(side=4, seed=0)
+    return DistributedRBCDDriver(meas, n, 4, Comm(), r=5,
+                                 partition="contiguous",
+                                 selection=selection,
+                                 acceleration=acceleration)
+
+
+def _golden_traces():
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                        "golden", "dist_driver_traces.json")
+    with open(path) as f:
+        return json.load(f)["runs"]
+
+
+@pytest.mark.parametrize("acceleration", [False, True],
+                         ids=["plain", "accel"])
+@pytest.mark.parametrize("selection", ["colored", "greedy",
+                                       "colored_greedy", "round_robin"])
+def test_dist_driver_dict_golden_trace(selection, acceleration):
+    """The dict path reproduces the traces recorded before the round
+    loop was unified (tests/golden/dist_driver_traces.json: grid3d side
+    4, 4 agents, contiguous, r=5, max_iters=250, default tol): same
+    iteration count and stop flag, every (cost, gradnorm) within 1e-9
+    relative (same math; the cost sum over agents may be reordered).
+    The round before each recorded crossing is at least 7.8e-3 away from
+    the tolerance, so the pinned counts do not sit on a rounding edge."""
+    want = _golden_traces()[selection + ("_accel" if acceleration else "")]
+    res = _ring_fixture_driver(selection, acceleration).run(max_iters=250)
+    assert res.iterations == want["iterations"]
+    assert res.converged == want["converged"]
+    assert len(res.trace) == len(want["trace"])
+    for (c, g), (cw, gw) in zip(res.trace, want["trace"]):
+        assert abs(c - cw) <= 1e-9 * abs(cw)
+        assert abs(g - gw) <= 1e-9 * abs(gw)
+
+
+def _run_chunked(chunk, **kw):
+    """Fresh colored driver with the readback width forced to `chunk`."""
+    drv = _ring_fixture_driver()
+    drv._readback_chunk = lambda gradnorm_tol: chunk
+    return drv.run(**kw)
+
+
+@pytest.fixture(scope="module")
+def chunk1_colored():
+    """Per-round readback runs the ring tests compare against."""
+    return {
+        "tol": _run_chunked(1, max_iters=250, gradnorm_tol=0.1),
+        "cap10": _run_chunked(1, max_iters=10, gradnorm_tol=0.1),
+        "tol0": _run_chunked(1, max_iters=20, gradnorm_tol=0.0),
+    }
+
+
+def test_readback_chunk_rule():
+    for sel, tol, want in (("colored", 0.1, 8), ("colored", 0.0, 16),
+                           ("round_robin", 0.0, 16),
+                           ("round_robin", 0.1, 1), ("greedy", 0.0, 1),
+                           ("greedy", 0.1, 1), ("colored_greedy", 0.0, 1),
+                           ("colored_greedy", 0.1, 1)):
+        assert _ring_fixture_driver(sel)._readback_chunk(tol) == want
+
+
+@pytest.mark.parametrize("chunk", [8, 5])
+def test_readback_ring_truncates_at_crossing(chunk1_colored, chunk):
+    """The loop runs on to the end of the chunk that holds the crossing
+    round (12: second chunk of 8, third chunk of 5) and then cuts
+    iterations and trace back to it. CPU math is deterministic and the
+    extra rounds come after the kept ones, so equality is exact."""
+    ref = chunk1_colored["tol"]
+    res = _run_chunked(chunk, max_iters=250, gradnorm_tol=0.1)
+    assert ref.converged and res.converged
+    assert res.iterations == 12
+    assert len(res.trace) == 12
+    assert res.trace == ref.trace
+    assert (res.final_cost, res.final_gradnorm) == res.trace[-1]
+
+
+def test_readback_ring_final_partial_flush(chunk1_colored):
+    ref = chunk1_colored["cap10"]
+    res = _run_chunked(8, max_iters=10, gradnorm_tol=0.1)
+    assert not res.converged
+    assert res.iterations == 10
+    assert len(res.trace) == 10
+    assert res.trace == ref.trace == chunk1_colored["tol"].trace[:10]
+
+
+def test_readback_ring_no_stop_test(chunk1_colored):
+    ref = chunk1_colored["tol0"]
+    res = _run_chunked(16, max_iters=20, gradnorm_tol=0.0)
+    assert not res.converged
+    assert res.iterations == 20
+    assert len(res.trace) == 20
+    assert res.trace == ref.trace
+
+
+def test_readback_ring_trace_file(tmp_path, chunk1_colored):
+    """The trace file gets one line per round read back, written at the
+    flush — before the stop test looks at the chunk. With chunk 8 and
+    the crossing at round 12 that is 16 lines: the result is truncated
+    to 12 entries, the file keeps the 4 rounds run past the crossing
+    (what the pipelined GPU path has always written)."""
+    path = tmp_path / "trace.csv"
+    res = _run_chunked(8, max_iters=250, gradnorm_tol=0.1,
+                       trace_file=str(path))
+    lines = path.read_text().splitlines()
+    assert res.iterations == 12
+    assert len(lines) == 16
+    assert lines[:12] == [f"{c:.10g},{g:.10g}" for c, g in res.trace]
+    # per-round readback stops writing at the crossing
+    path1 = tmp_path / "trace1.csv"
+    _run_chunked(1, max_iters=250, gradnorm_tol=0.1,
+                 trace_file=str(path1))
+    assert path1.read_text().splitlines() == lines[:12]

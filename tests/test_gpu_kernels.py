@@ -460,6 +460,34 @@ def test_bench_episode_restore_deterministic():
         assert abs(a[1] - b[1]) <= 1e-9 * max(1.0, abs(a[1]))
 
 
+def test_packed_readback_ring_matches_per_round():
+    """Packed path, colored, tol 0.1: the default 8-round readback ring
+    (runs past the crossing, then truncates) must report the same
+    iterations and trace as reading back every round."""
+    from dpo_amd.comm import Comm
+    from dpo_amd.dist_driver import DistributedRBCDDriver
+    from dpo_amd.synthetic import grid3d
+    meas, n = grid3d(side=4, seed=0)
+
+    def run(chunk):
+        drv = DistributedRBCDDriver(meas, n, 4, Comm(), r=5,
+                                    partition="contiguous",
+                                    selection="colored", device=DEV)
+        if chunk is None:
+            assert drv._readback_chunk(0.1) == 8
+        else:
+            drv._readback_chunk = lambda gradnorm_tol: chunk
+        return drv.run(max_iters=250, gradnorm_tol=0.1)
+
+    ring, each = run(None), run(1)
+    assert ring.converged and each.converged
+    assert ring.iterations == each.iterations
+    assert len(ring.trace) == len(each.trace) == ring.iterations
+    for (ca, ga), (cb, gb) in zip(ring.trace, each.trace):
+        assert abs(ca - cb) <= 1e-9 * abs(cb)
+        assert abs(ga - gb) <= 1e-9 * abs(gb)
+
+
 def test_hess_wide_matches_narrow():
     """k_hess_wide (element-per-thread, large-agent layout) must produce
     the same solve trajectory as k_hess_fused (thread-per-pose). Run in
