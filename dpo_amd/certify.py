@@ -14,7 +14,9 @@ saddle-escape step at rank r + 1.
 Limitations: CERTIFIED rests on the Lanczos residual bound
 |beta_m u_m| for the smallest Ritz pair, not on a factorisation-based
 interval proof; and graphs with a tiny spectral gap can need more steps
-than `max_iters` and then return INCONCLUSIVE.
+than `max_iters` and then return INCONCLUSIVE. With `basis_size` the
+basis is a fixed window (thick-restart Lanczos), so `max_iters` is a time
+budget and no longer a memory one.
 """
 from __future__ import annotations
 
@@ -26,8 +28,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .ops.cpu_ref import (CERT_COUNT, CERT_FLAG, CERT_HDR, CERT_TOL,
-                          cert_check_shape)
+from .ops.cpu_ref import (CERT_COUNT, CERT_FLAG, CERT_HDR, CERT_KEEP_MAX,
+                          CERT_TOL, cert_check_shape)
 from .quadratic import (BSRMatrix, QuadraticProblem,
                         assemble_connection_laplacian)
 
@@ -57,17 +59,23 @@ class CertificateResult:
     grad_norm: float       # ||S @ Xt||_F
     iterations: int        # Lanczos steps taken
     direction: Optional[Tensor]  # (N,) unit Ritz vector of lambda_min
+    restarts: int = 0      # thick restarts taken (basis_size path)
+    restarted: bool = False  # basis_size was given
 
     def as_dict(self) -> dict:
-        """JSON-safe summary (no direction; values not computed are None)."""
+        """JSON-safe summary (no direction; values not computed are None).
+        `certificate_restarts` appears only for a basis_size run."""
         def num(x):
             return None if x != x else x
-        return {"certificate": self.status.value,
-                "lambda_min": num(self.lambda_min),
-                "lambda_max": num(self.lambda_max),
-                "certificate_residual": num(self.residual),
-                "certificate_grad_norm": self.grad_norm,
-                "certificate_iterations": self.iterations}
+        out = {"certificate": self.status.value,
+               "lambda_min": num(self.lambda_min),
+               "lambda_max": num(self.lambda_max),
+               "certificate_residual": num(self.residual),
+               "certificate_grad_norm": self.grad_norm,
+               "certificate_iterations": self.iterations}
+        if self.restarted:
+            out["certificate_restarts"] = self.restarts
+        return out
 
 
 class BasisBudgetError(MemoryError):
@@ -117,13 +125,69 @@ def _ritz(alpha: np.ndarray, beta: np.ndarray):
             float(evals[-1]), float(bk * abs(evecs[-1, -1])))
 
 
+def _ritz_dense(T: np.ndarray, beta_last: float):
+    """`_ritz` for the dense projected matrix T (k x k) of a thick-restart
+    window; beta_last couples its last basis vector to the next one."""
+    evals, evecs = np.linalg.eigh(T)
+    bk = abs(beta_last)
+    return (float(evals[0]), evecs[:, 0], float(bk * abs(evecs[-1, 0])),
+            float(evals[-1]), float(bk * abs(evecs[-1, -1])))
+
+
+def default_keep(basis_size: int) -> Tuple[int, int]:
+    """Ritz pairs kept at a restart of a window of b vectors: the two
+    largest (one for b < 6) and the b // 2 - k_hi smallest, at least one
+    and at most what the contraction kernel's CERT_KEEP_MAX columns
+    leave. Half the window is the usual thick-restart compromise between
+    progress per restart and steps between restarts."""
+    k_hi = 2 if basis_size >= 6 else 1
+    k_lo = min(max(1, basis_size // 2 - k_hi), CERT_KEEP_MAX - k_hi)
+    return k_lo, k_hi
+
+
+def _check_keep(basis_size: int,
+                keep: Optional[Tuple[int, int]]) -> Tuple[int, int]:
+    if basis_size < 4:
+        raise ValueError(f"basis_size={basis_size}: a restart window needs "
+                         "at least 4 vectors")
+    k_lo, k_hi = default_keep(basis_size) if keep is None else keep
+    if (k_lo < 1 or k_hi < 1 or k_lo + k_hi + 2 > basis_size
+            or k_lo + k_hi > CERT_KEEP_MAX):
+        raise ValueError(
+            f"keep=({k_lo}, {k_hi}) with basis_size={basis_size}: need "
+            "k_lo >= 1, k_hi >= 1, k_lo + k_hi + 2 <= basis_size and "
+            f"k_lo + k_hi <= {CERT_KEEP_MAX}")
+    return int(k_lo), int(k_hi)
+
+
+def _thick_restart(T: np.ndarray, beta_last: float,
+                   keep: Tuple[int, int]) -> Tuple[np.ndarray, np.ndarray]:
+    """Restart of a full window with projected matrix T (b x b): the
+    (b, k) coefficients C of the kept Ritz vectors (k_lo smallest, k_hi
+    largest) and the new projected matrix, diag(theta_1..theta_k) with
+    the arrowhead s_i = beta_last * Y[b - 1, i] in row and column k and
+    zero (to be filled by the next steps) below."""
+    b = T.shape[0]
+    k_lo, k_hi = keep
+    evals, Y = np.linalg.eigh(T)
+    idx = list(range(k_lo)) + list(range(b - k_hi, b))
+    k = len(idx)
+    Tn = np.zeros_like(T)
+    Tn[np.arange(k), np.arange(k)] = evals[idx]
+    Tn[:k, k] = Tn[k, :k] = beta_last * Y[b - 1, idx]
+    return np.ascontiguousarray(Y[:, idx]), Tn
+
+
 def certify_solution(measurements, n: int, d: int, Xt: Tensor, *,
                      weights: Optional[Sequence[float]] = None,
                      eta: Optional[float] = None,
                      grad_tol: Optional[float] = None,
                      max_iters: int = 512, check_every: int = 16,
                      seed: int = 0,
-                     basis_budget_bytes: int = 2 << 30) -> CertificateResult:
+                     basis_budget_bytes: int = 2 << 30,
+                     basis_size: Optional[int] = None,
+                     keep: Optional[Tuple[int, int]] = None
+                     ) -> CertificateResult:
     """Certify that the lifted iterate Xt (N, r), N = n (d+1), is a global
     minimiser of the rank-relaxed problem of `measurements`.
 
@@ -143,6 +207,19 @@ def certify_solution(measurements, n: int, d: int, Xt: Tensor, *,
               the basis costs N * (m + 1) doubles, m = min(max_iters, N);
               BasisBudgetError is raised before anything is allocated
               when that exceeds the budget.
+    basis_size
+              None: the path above. b >= 4: thick-restart Lanczos in a
+              window of b vectors. The basis costs N * (b + 1) doubles
+              whatever max_iters is; max_iters counts operator
+              applications across restarts and may exceed b and N. Full
+              reorthogonalisation stays, inside the window. When the
+              window is full it is contracted to the kept Ritz vectors
+              plus the residual vector and the recurrence carries on.
+    keep      (k_lo, k_hi): the k_lo smallest and k_hi largest Ritz pairs
+              survive a restart; the large end is kept because CERTIFIED
+              waits for lambda_max to converge. Default `default_keep(b)`.
+              ValueError unless k_lo, k_hi >= 1, k_lo + k_hi + 2 <= b and
+              k_lo + k_hi <= 16 (the contraction kernel's column bound).
 
     Decision, in this order: NOT_CRITICAL when the gradient norm exceeds
     grad_tol (Lanczos is skipped); NOT_OPTIMAL as soon as the smallest
@@ -157,13 +234,20 @@ def certify_solution(measurements, n: int, d: int, Xt: Tensor, *,
     assert Xt.dim() == 2 and Xt.shape[0] == n * (d + 1)
     N, r = Xt.shape
     cert_check_shape(d, r)
-    m = int(min(max_iters, N))
+    if basis_size is None:
+        if keep is not None:
+            raise ValueError("keep is only meaningful with basis_size")
+        m = int(min(max_iters, N))
+    else:
+        m = int(basis_size)
+        keep = _check_keep(m, keep)
     need = 8 * N * (m + 1)
     if need > basis_budget_bytes:
         raise BasisBudgetError(
             f"Lanczos basis needs {need} bytes (N={N}, {m + 1} vectors) "
             f"but basis_budget_bytes={basis_budget_bytes}; raise the "
-            "budget or lower max_iters")
+            "budget or " + ("lower max_iters or pass basis_size"
+                            if basis_size is None else "lower basis_size"))
     dev = Xt.device
     Xt = Xt.to(torch.float64).contiguous()
     if isinstance(weights, Tensor):
@@ -178,7 +262,8 @@ def certify_solution(measurements, n: int, d: int, Xt: Tensor, *,
         grad_tol = 1e-4 * float(np.sqrt(bound))
     if not grad_norm <= grad_tol:
         return CertificateResult(CertificateStatus.NOT_CRITICAL, nan, nan,
-                                 nan, grad_norm, 0, None)
+                                 nan, grad_norm, 0, None, 0,
+                                 basis_size is not None)
 
     be = ops.backend_for(Xt)
     g = torch.Generator().manual_seed(seed)
@@ -190,13 +275,61 @@ def certify_solution(measurements, n: int, d: int, Xt: Tensor, *,
     ctl_host[CERT_TOL] = BREAKDOWN_TOL * bound
     ctl = ctl_host.to(dev)
 
-    def finish(status, k, theta, u, resid, lmax):
-        y = (u.to(dev) @ V[:k])
+    def finish(status, k, theta, u, resid, lmax, steps=None, restarts=0):
+        y = (torch.from_numpy(u.copy()).to(dev) @ V[:k])
         y /= torch.linalg.norm(y)
-        return CertificateResult(status, theta, resid, lmax, grad_norm, k, y)
+        return CertificateResult(status, theta, resid, lmax, grad_norm,
+                                 k if steps is None else steps, y,
+                                 restarts, basis_size is not None)
+
+    def decide(theta, resid, lmax, resid_max, exact):
+        lmax_ok = exact or resid_max <= LMAX_RTOL * abs(lmax)
+        eta_now = eta if eta is not None else 1e-6 * (
+            lmax if lmax_ok else bound)
+        if theta < -eta_now:
+            return CertificateStatus.NOT_OPTIMAL
+        if exact or (lmax_ok and resid <= eta_now):
+            return CertificateStatus.CERTIFIED
+        return CertificateStatus.INCONCLUSIVE
+
+    if basis_size is not None:
+        # Thick restart: a window of m = basis_size vectors whose first
+        # `pos` columns are filled; T is its dense projected matrix.
+        T = np.zeros((m, m))
+        pos = total = restarts = 0
+        while True:
+            nsteps = min(check_every, m - pos, max_iters - total)
+            be.cert_lanczos_window(Q, lam, V, ctl, pos, nsteps)
+            h = ctl.cpu().numpy()  # the one device-to-host read per batch
+            k = int(h[CERT_COUNT])
+            broke = h[CERT_FLAG] != 0.0
+            alpha, beta = h[CERT_HDR:CERT_HDR + m], h[CERT_HDR + m:]
+            for j in range(pos, k):
+                T[j, j] = alpha[j]
+                if j + 1 < m:
+                    T[j, j + 1] = T[j + 1, j] = beta[j]
+            total += k - pos
+            pos = k
+            theta, u, resid, lmax, resid_max = _ritz_dense(
+                T[:k, :k], beta[k - 1])
+            status = decide(theta, resid, lmax, resid_max, bool(broke))
+            if (status != CertificateStatus.INCONCLUSIVE or broke
+                    or total >= max_iters):
+                return finish(status, k, theta, u, resid, lmax, total,
+                              restarts)
+            if k == m:
+                C, T = _thick_restart(T, beta[m - 1], keep)
+                be.cert_contract(V, torch.from_numpy(C))
+                restarts += 1
+                pos = C.shape[1]
+                # the step count, and the beta slot the next k_cert_apply
+                # reads: CGS2 removes the arrowhead component by itself
+                h = h.copy()
+                h[CERT_COUNT] = pos
+                h[CERT_HDR + m + pos - 1] = 0.0
+                ctl.copy_(torch.from_numpy(h))
 
     done = 0
-    status = CertificateStatus.INCONCLUSIVE
     while True:
         nsteps = min(check_every, m - done)
         be.cert_lanczos_steps(Q, lam, V, ctl, done, nsteps)
@@ -206,17 +339,10 @@ def certify_solution(measurements, n: int, d: int, Xt: Tensor, *,
         done += nsteps
         theta, u, resid, lmax, resid_max = _ritz(
             h[CERT_HDR:CERT_HDR + k], h[CERT_HDR + m:CERT_HDR + m + k])
-        exact = bool(broke)     # beta_k = 0: the Ritz values are exact
-        lmax_ok = exact or resid_max <= LMAX_RTOL * abs(lmax)
-        eta_now = eta if eta is not None else 1e-6 * (
-            lmax if lmax_ok else bound)
-        if theta < -eta_now:
-            status = CertificateStatus.NOT_OPTIMAL
-        elif exact or (lmax_ok and resid <= eta_now):
-            status = CertificateStatus.CERTIFIED
+        # broke: beta_k = 0, the Ritz values are exact
+        status = decide(theta, resid, lmax, resid_max, bool(broke))
         if status != CertificateStatus.INCONCLUSIVE or broke or done >= m:
-            return finish(status, k, theta, torch.from_numpy(u.copy()),
-                          resid, lmax)
+            return finish(status, k, theta, u, resid, lmax)
 
 
 def escape_direction(Q: BSRMatrix, Xt: Tensor, direction: Tensor, *,

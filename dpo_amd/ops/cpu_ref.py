@@ -193,3 +193,51 @@ def cert_lanczos_steps(Q, lam: Tensor, V: Tensor, ctl: Tensor,
             ctl[CERT_FLAG] = 1.0
             return
         V[j + 1] = w / beta
+
+
+# Thick-restart window (certify_solution(basis_size=b)): the same step
+# inside a basis of b + 1 rows. After a restart that kept k Ritz vectors
+# the caller sets ctl[CERT_COUNT] = k and zeroes beta[k - 1]; step k then
+# needs no special case, because CGS2 removes the arrowhead component.
+# `gram` selects the HIP Gram kernel and has no meaning on the CPU.
+CERT_KEEP_MAX = 16      # k_cert_contract's compile-time column bound
+CERT_BLOCK = 256        # threads per block, and most partials per sum
+
+
+def cert_partials(N: int) -> int:
+    """Blocks (= per-block partial slots) the certificate kernels use
+    for a length-N vector."""
+    return min(-(-N // CERT_BLOCK), CERT_BLOCK)
+
+
+def cert_lanczos_window(Q, lam: Tensor, V: Tensor, ctl: Tensor,
+                        first_step: int, nsteps: int,
+                        gram: Optional[str] = None) -> None:
+    """cert_lanczos_steps on the (b + 1, N) window basis V."""
+    cert_lanczos_steps(Q, lam, V, ctl, first_step, nsteps)
+
+
+def cert_gram_split(V: Tensor, w: Tensor, c: Tensor,
+                    ctl: Optional[Tensor] = None,
+                    alpha_part: Optional[Tensor] = None,
+                    alpha: Optional[Tensor] = None) -> None:
+    """c[:] = V[:len(c)] @ w and, with `alpha`, alpha[0] = the sum of the
+    cert_partials(N) partials in alpha_part. A raised ctl[CERT_FLAG]
+    leaves both untouched."""
+    if ctl is not None and float(ctl[CERT_FLAG]) != 0.0:
+        return
+    c.copy_(V[:c.numel()] @ w)
+    if alpha is not None:
+        alpha[0] = alpha_part[:cert_partials(w.numel())].sum()
+
+
+def cert_contract(V: Tensor, C: Tensor) -> None:
+    """Thick-restart contraction of the (b + 1, N) basis with the (b, k)
+    Ritz coefficients C: V[:k] = C^T @ V[:b] (out of place, then stored)
+    and V[k] = V[b]. Rows past k keep stale data."""
+    b, k = C.shape
+    assert V.shape[0] == b + 1 and 1 <= k <= min(b, CERT_KEEP_MAX)
+    new = C.T.to(V.dtype) @ V[:b]
+    carry = V[b].clone()
+    V[:k] = new
+    V[k] = carry

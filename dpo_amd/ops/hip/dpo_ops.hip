@@ -2955,6 +2955,92 @@ __global__ void k_cert_gram(const double* __restrict__ V,
   }
 }
 
+// Row-split c = V^T w for the restarted path: the rows of N are divided
+// over the grid, each block handles its rows for all ncols columns in
+// tiles of CERT_GRAM_CT columns (w is re-read once per tile, 1/CT of the
+// V traffic) and stores one partial per (column, block) at
+// gpart[col * gridDim.x + block]. A tail tile clamps the column index
+// and discards the duplicate sums. k_cert_gram_finish sums the slots.
+#define CERT_GRAM_CT 8
+__global__ void k_cert_gram_split(const double* __restrict__ V,
+                                  const double* __restrict__ w,
+                                  double* __restrict__ gpart, int ncols,
+                                  long N, const double* __restrict__ cc) {
+  if (cert_off(cc)) return;
+  for (int c0 = 0; c0 < ncols; c0 += CERT_GRAM_CT) {
+    const double* Vc[CERT_GRAM_CT];
+    #pragma unroll
+    for (int c = 0; c < CERT_GRAM_CT; ++c) {
+      const int col = c0 + c < ncols ? c0 + c : ncols - 1;
+      Vc[c] = V + (size_t)col * N;
+    }
+    double acc[CERT_GRAM_CT];
+    #pragma unroll
+    for (int c = 0; c < CERT_GRAM_CT; ++c) acc[c] = 0.0;
+    for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+         row += (long)gridDim.x * CERT_BS) {
+      const double wr = w[row];
+      #pragma unroll
+      for (int c = 0; c < CERT_GRAM_CT; ++c)
+        acc[c] = fma(Vc[c][row], wr, acc[c]);
+    }
+    #pragma unroll
+    for (int c = 0; c < CERT_GRAM_CT; ++c) {
+      const double s = cert_block_sum(acc[c]);
+      if (threadIdx.x == 0 && c0 + c < ncols)
+        gpart[(size_t)(c0 + c) * gridDim.x + blockIdx.x] = s;
+    }
+  }
+}
+
+// c[col] = fixed-order sum of column col's ngrid row-split partials, one
+// workgroup per column; block 0 of the first pass also finalises alpha
+// from k_cert_apply's partials, as k_cert_gram does.
+__global__ void k_cert_gram_finish(const double* __restrict__ gpart,
+                                   int ngrid, double* __restrict__ c,
+                                   const double* __restrict__ cc,
+                                   const double* __restrict__ part,
+                                   int npart,
+                                   double* __restrict__ alpha_out) {
+  if (cert_off(cc)) return;
+  const double s =
+      cert_sum_partials(gpart + (size_t)blockIdx.x * ngrid, ngrid);
+  if (threadIdx.x == 0) c[blockIdx.x] = s;
+  if (alpha_out != nullptr && blockIdx.x == 0) {
+    const double a = cert_sum_partials(part, npart);
+    if (threadIdx.x == 0) alpha_out[0] = a;
+  }
+}
+
+// Thick-restart basis contraction, in place: V[0..k) <- C^T V[0..b),
+// V[k] <- V[b]. V is b + 1 contiguous vectors of length N; C is b rows of
+// CERT_KEEP_MAX coefficients (columns >= k are zero padding). One thread
+// owns row index i: it reads V[0..b][i] (coalesced across the wave) into
+// CERT_KEEP_MAX register accumulators and stores only after its last
+// load, and no other thread touches index i, so in place is safe. V is
+// deliberately not __restrict__: the stores alias the loads.
+#define CERT_KEEP_MAX 16
+__global__ void k_cert_contract(double* V, const double* __restrict__ C,
+                                int b, int k, long N) {
+  for (long i = (long)blockIdx.x * CERT_BS + threadIdx.x; i < N;
+       i += (long)gridDim.x * CERT_BS) {
+    double acc[CERT_KEEP_MAX];
+    #pragma unroll
+    for (int c = 0; c < CERT_KEEP_MAX; ++c) acc[c] = 0.0;
+    for (int j = 0; j < b; ++j) {
+      const double x = V[(size_t)j * N + i];
+      #pragma unroll
+      for (int c = 0; c < CERT_KEEP_MAX; ++c)
+        acc[c] = fma(C[j * CERT_KEEP_MAX + c], x, acc[c]);
+    }
+    const double carry = V[(size_t)b * N + i];
+    #pragma unroll
+    for (int c = 0; c < CERT_KEEP_MAX; ++c)
+      if (c < k) V[(size_t)c * N + i] = acc[c];
+    V[(size_t)k * N + i] = carry;
+  }
+}
+
 // w -= V c; with part != nullptr also the block partials of ||w||^2.
 __global__ void k_cert_sub(const double* __restrict__ V,
                            const double* __restrict__ c,
@@ -3036,6 +3122,57 @@ static void launch_cert_apply(const int* rp, const int* ci,
     dpo_bad_shape(d, -1);
 }
 
+static void launch_cert_gram_split(const double* V, const double* w,
+                                   double* c, double* gpart,
+                                   const double* cc, const double* part,
+                                   double* alpha_out, int ncols, long N,
+                                   hipStream_t s) {
+  const int grid = cert_grid(N);
+  hipLaunchKernelGGL(k_cert_gram_split, dim3(grid), dim3(CERT_BS), 0, s, V,
+                     w, gpart, ncols, N, cc);
+  hipLaunchKernelGGL(k_cert_gram_finish, dim3(ncols), dim3(CERT_BS), 0, s,
+                     (const double*)gpart, grid, c, cc, part, grid,
+                     alpha_out);
+}
+
+// Lanczos steps first_step .. first_step + nsteps - 1 (below m) on the
+// stream. gpart == nullptr: c = V^T w by k_cert_gram, one workgroup per
+// column; otherwise by the row-split pair with gpart as its slots.
+static void cert_enqueue_steps(const int* row_ptr, const int* col_idx,
+                               const double* vals, const double* lam,
+                               double* V, double* w, double* cvec,
+                               double* part, double* gpart, double* cc,
+                               int n, int d, int m, int first_step,
+                               int nsteps, hipStream_t s) {
+  const long N = (long)n * (d + 1);
+  const int grid = cert_grid(N);
+  for (int j = first_step; j < first_step + nsteps && j < m; ++j) {
+    const double* vj = V + (size_t)j * N;
+    const double* vp = j > 0 ? V + (size_t)(j - 1) * N : nullptr;
+    const double* bp = j > 0 ? cc + CC_HDR + m + j - 1 : nullptr;
+    launch_cert_apply(row_ptr, col_idx, vals, lam, vj, vp, bp, w, part, n,
+                      d, cc, s);
+    // CGS2: two classical Gram-Schmidt passes against columns 0..j
+    for (int pass = 0; pass < 2; ++pass) {
+      double* alpha_out = pass == 0 ? cc + CC_HDR + j : nullptr;
+      if (gpart != nullptr)
+        launch_cert_gram_split(V, w, cvec, gpart, cc, part, alpha_out,
+                               j + 1, N, s);
+      else
+        hipLaunchKernelGGL(k_cert_gram, dim3(j + 1), dim3(CERT_BS), 0, s,
+                           (const double*)V, (const double*)w, cvec, N,
+                           (const double*)cc, (const double*)part, grid,
+                           alpha_out);
+      hipLaunchKernelGGL(k_cert_sub, dim3(grid), dim3(CERT_BS), 0, s,
+                         (const double*)V, (const double*)cvec, w, j + 1, N,
+                         (const double*)cc, pass == 1 ? part : nullptr);
+    }
+    hipLaunchKernelGGL(k_cert_norm, dim3(grid), dim3(CERT_BS), 0, s,
+                       (const double*)w, V + (size_t)(j + 1) * N, N, cc,
+                       (const double*)part, grid, j, m);
+  }
+}
+
 extern "C" {
 
 // lam (n, d, d) and res_out[0] = ||QX - Lambda X||_F^2 from X and
@@ -3073,32 +3210,46 @@ void dpo_cert_lanczos(const int* row_ptr, const int* col_idx,
                       double* w, double* cvec, double* part, double* cc,
                       int n, int d, int m, int first_step, int nsteps,
                       void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const long N = (long)n * (d + 1);
-  const int grid = cert_grid(N);
-  for (int j = first_step; j < first_step + nsteps && j < m; ++j) {
-    const double* vj = V + (size_t)j * N;
-    const double* vp = j > 0 ? V + (size_t)(j - 1) * N : nullptr;
-    const double* bp = j > 0 ? cc + CC_HDR + m + j - 1 : nullptr;
-    launch_cert_apply(row_ptr, col_idx, vals, lam, vj, vp, bp, w, part, n,
-                      d, cc, s);
-    // CGS2: two classical Gram-Schmidt passes against columns 0..j
-    for (int pass = 0; pass < 2; ++pass) {
-      hipLaunchKernelGGL(k_cert_gram, dim3(j + 1), dim3(CERT_BS), 0, s,
-                         (const double*)V, (const double*)w, cvec, N,
-                         (const double*)cc, (const double*)part, grid,
-                         pass == 0 ? cc + CC_HDR + j : nullptr);
-      hipLaunchKernelGGL(k_cert_sub, dim3(grid), dim3(CERT_BS), 0, s,
-                         (const double*)V, (const double*)cvec, w, j + 1, N,
-                         (const double*)cc, pass == 1 ? part : nullptr);
-    }
-    hipLaunchKernelGGL(k_cert_norm, dim3(grid), dim3(CERT_BS), 0, s,
-                       (const double*)w, V + (size_t)(j + 1) * N, N, cc,
-                       (const double*)part, grid, j, m);
-  }
+  cert_enqueue_steps(row_ptr, col_idx, vals, lam, V, w, cvec, part,
+                     nullptr, cc, n, d, m, first_step, nsteps,
+                     (hipStream_t)stream);
+}
+
+// The same steps inside a thick-restart window of b = m columns, with
+// the row-split Gram: gpart holds (m + 1) * CERT_MAX_PART doubles. After
+// a restart that kept k Ritz vectors the host resets the step count to
+// k and zeroes beta[k - 1]; step k then needs no special case.
+void dpo_cert_lanczos_split(const int* row_ptr, const int* col_idx,
+                            const double* vals, const double* lam,
+                            double* V, double* w, double* cvec,
+                            double* part, double* gpart, double* cc, int n,
+                            int d, int m, int first_step, int nsteps,
+                            void* stream) {
+  cert_enqueue_steps(row_ptr, col_idx, vals, lam, V, w, cvec, part, gpart,
+                     cc, n, d, m, first_step, nsteps, (hipStream_t)stream);
+}
+
+// Stand-alone row-split Gram: c[0..ncols) = V^T w and, with alpha_out,
+// alpha_out[0] = sum of the cert_grid(N) partials in part. gpart: ncols *
+// CERT_MAX_PART doubles. cc may be null (no guard).
+void dpo_cert_gram_split(const double* V, const double* w, double* c,
+                         double* gpart, const double* cc,
+                         const double* part, double* alpha_out, int ncols,
+                         long N, void* stream) {
+  launch_cert_gram_split(V, w, c, gpart, cc, part, alpha_out, ncols, N,
+                         (hipStream_t)stream);
+}
+
+// Thick-restart contraction V[0..k) <- C^T V[0..b), V[k] <- V[b], in
+// place; C is b x CERT_KEEP_MAX row-major, zero beyond column k.
+void dpo_cert_contract(double* V, const double* C, int b, int k, long N,
+                       void* stream) {
+  hipLaunchKernelGGL(k_cert_contract, dim3(cert_grid(N)), dim3(CERT_BS), 0,
+                     (hipStream_t)stream, V, C, b, k, N);
 }
 
 int dpo_cert_ctrl_header() { return CC_HDR; }
 int dpo_cert_max_part() { return CERT_MAX_PART; }
+int dpo_cert_keep_max() { return CERT_KEEP_MAX; }
 
 }  // extern "C"

@@ -647,3 +647,94 @@ def cert_lanczos_steps(Q, lam: Tensor, V: Tensor, ctl: Tensor,
     _lib.dpo_cert_lanczos(_p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals),
                           _p(lam), _p(V), _p(w), _p(cvec), _p(part),
                           _p(ctl), n, d, m, first_step, nsteps, _stream(V))
+
+
+# ---- thick-restart window (interface mirrors cpu_ref) ----------------
+_lib.dpo_cert_lanczos_split.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c,
+                                        _c, _i, _i, _i, _i, _i, _c]
+_lib.dpo_cert_gram_split.argtypes = [_c, _c, _c, _c, _c, _c, _c, _i, _l,
+                                     _c]
+_lib.dpo_cert_contract.argtypes = [_c, _c, _i, _i, _l, _c]
+_lib.dpo_cert_keep_max.restype = _i
+
+from .cpu_ref import CERT_KEEP_MAX, cert_partials  # noqa: E402
+
+assert _lib.dpo_cert_keep_max() == CERT_KEEP_MAX
+
+# Below this N the window path keeps k_cert_gram (one workgroup per
+# column). Measured step time with 64 stored vectors, column / split in
+# us (profiles/cert_gram_ab.json, docs/DESIGN.md §14): N = 864 30 / 82,
+# 10 976 50 / 84, 42 592 133 / 89, 4e6 16 130 / 4 389. The split step is
+# flat near 85 us up to N ~ 4e4 (few blocks, each with 8 serial block
+# sums per column tile, and two more launches); the column step grows
+# with N and crosses it near 2.5e4 by linear interpolation. N is fixed
+# per problem, so the choice is too.
+CERT_SPLIT_MIN_N = 24576
+
+
+def cert_lanczos_window(Q, lam: Tensor, V: Tensor, ctl: Tensor,
+                        first_step: int, nsteps: int,
+                        gram: Optional[str] = None) -> None:
+    """cert_lanczos_steps on the (b + 1, N) window basis of the restarted
+    path. gram: "split" (row-split Gram), "column" (k_cert_gram), or
+    None to choose by N (CERT_SPLIT_MIN_N)."""
+    n, d = lam.shape[0], lam.shape[1]
+    N = V.shape[1]
+    if gram is None:
+        gram = "split" if N >= CERT_SPLIT_MIN_N else "column"
+    assert gram in ("split", "column")
+    if gram == "column":
+        return cert_lanczos_steps(Q, lam, V, ctl, first_step, nsteps)
+    _chk(lam); _chk(V); _chk(ctl); _chk_q(Q, V)
+    cert_check_shape(d, None)
+    m = V.shape[0] - 1
+    assert Q.n == n and Q.dh == d + 1 and N == n * (d + 1)
+    assert ctl.numel() == CERT_HDR + 2 * m
+    assert 0 <= first_step and nsteps >= 0 and first_step + nsteps <= m
+    dev = V.device
+    w = torch.empty(N, dtype=torch.float64, device=dev)
+    cvec = torch.empty(m + 1, dtype=torch.float64, device=dev)
+    part = torch.empty(_CERT_PART, dtype=torch.float64, device=dev)
+    gpart = torch.empty((m + 1) * _CERT_PART, dtype=torch.float64,
+                        device=dev)
+    _lib.dpo_cert_lanczos_split(
+        _p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals), _p(lam), _p(V), _p(w),
+        _p(cvec), _p(part), _p(gpart), _p(ctl), n, d, m, first_step,
+        nsteps, _stream(V))
+
+
+def cert_gram_split(V: Tensor, w: Tensor, c: Tensor,
+                    ctl: Optional[Tensor] = None,
+                    alpha_part: Optional[Tensor] = None,
+                    alpha: Optional[Tensor] = None) -> None:
+    """c[:] = V[:len(c)] @ w by the row-split Gram kernels and, with
+    `alpha`, alpha[0] = the fixed-order sum of the cert_partials(N)
+    partials in alpha_part. A raised ctl flag leaves both untouched."""
+    _chk(V); _chk(w); _chk(c)
+    ncols, N = c.numel(), w.numel()
+    assert V.dim() == 2 and V.shape[1] == N and 1 <= ncols <= V.shape[0]
+    if ctl is not None:
+        _chk(ctl)
+        assert ctl.numel() >= CERT_HDR
+    if alpha is not None:
+        _chk(alpha); _chk(alpha_part)
+        assert alpha.numel() == 1
+        assert alpha_part.numel() >= cert_partials(N)
+    gpart = torch.empty(ncols * _CERT_PART, dtype=torch.float64,
+                        device=V.device)
+    _lib.dpo_cert_gram_split(_p(V), _p(w), _p(c), _p(gpart), _p(ctl),
+                             _p(alpha_part), _p(alpha), ncols, N,
+                             _stream(V))
+
+
+def cert_contract(V: Tensor, C: Tensor) -> None:
+    """Thick-restart contraction of the (b + 1, N) device basis with the
+    (b, k) Ritz coefficients C (host or device), in place:
+    V[:k] = C^T @ V[:b], V[k] = V[b]. Rows past k keep stale data."""
+    _chk(V)
+    b, k = C.shape
+    assert V.shape[0] == b + 1 and 1 <= k <= min(b, CERT_KEEP_MAX)
+    Cp = torch.zeros(b, CERT_KEEP_MAX, dtype=torch.float64)
+    Cp[:, :k] = C.detach().to("cpu", torch.float64)
+    Cd = Cp.to(V.device)
+    _lib.dpo_cert_contract(_p(V), _p(Cd), b, k, V.shape[1], _stream(V))

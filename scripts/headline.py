@@ -38,6 +38,11 @@ def main():
                     help="after the run, certify global optimality of the "
                          "lifted iterate (min eigenvalue of Q - Lambda) and "
                          "add the verdict to the JSON line")
+    ap.add_argument("--cert-basis", type=int, default=None, metavar="B",
+                    help="with --certify: thick-restart Lanczos in a window "
+                         "of B vectors (basis memory N (B + 1) doubles)")
+    ap.add_argument("--cert-max-iters", type=int, default=None, metavar="M",
+                    help="with --certify: Lanczos step budget (default 512)")
     args = ap.parse_args()
 
     from dpo_amd.io_g2o import load_dataset
@@ -88,10 +93,15 @@ def main():
               else drv._gather_global_x().reshape(-1, args.r))
         if Xt is not None and rank == 0:
             from dpo_amd.certify import certify_solution
+            kw = {}
+            if args.cert_basis is not None:
+                kw["basis_size"] = args.cert_basis
+            if args.cert_max_iters is not None:
+                kw["max_iters"] = args.cert_max_iters
             t_cert = time.perf_counter()
             cert = certify_solution(
                 meas, n, meas[0].d,
-                Xt.detach().to(torch.device(args.device)))
+                Xt.detach().to(torch.device(args.device)), **kw)
             out.update(cert.as_dict())
             out["certificate_s"] = time.perf_counter() - t_cert
     if rank == 0:

@@ -24,6 +24,11 @@ def main():
                     help="certify global optimality of the result (min "
                          "eigenvalue of Q - Lambda) and add the verdict to "
                          "the JSON line")
+    ap.add_argument("--cert-basis", type=int, default=None, metavar="B",
+                    help="with --certify: thick-restart Lanczos in a window "
+                         "of B vectors (basis memory N (B + 1) doubles)")
+    ap.add_argument("--cert-max-iters", type=int, default=None, metavar="M",
+                    help="with --certify: Lanczos step budget (default 512)")
     args = ap.parse_args()
 
     from dpo_amd.agent import PGOAgent
@@ -58,7 +63,12 @@ def main():
         # r = d: the lifted iterate is the trajectory itself, transposed
         Xt = torch.from_numpy(np.ascontiguousarray(Topt.T)).to(
             torch.device(args.device))
-        cert = certify_solution(meas, n, d, Xt)
+        kw = {}
+        if args.cert_basis is not None:
+            kw["basis_size"] = args.cert_basis
+        if args.cert_max_iters is not None:
+            kw["max_iters"] = args.cert_max_iters
+        cert = certify_solution(meas, n, d, Xt, **kw)
         out.update(cert.as_dict())
     print(json.dumps(out))
     if args.dump_trajectory:
