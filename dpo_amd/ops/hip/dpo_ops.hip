@@ -144,7 +144,24 @@ __device__ __forceinline__ bool fanin_last_block(double* ctrl) {
 // L2-visibly (the next kernel's dispatch acquire makes them visible to
 // all CUs).
 enum CtrlFuse { CF_NONE = 0, CF_Z0 = 1, CF_ALPHA = 2, CF_RR = 3,
-                CF_BETA = 4 };
+                CF_BETA = 4,
+                // tails of the solve head, the candidate evaluation and
+                // the per-round evaluation (bodies further down)
+                CF_INIT = 5, CF_ACCEPT = 6, CF_ACCEPT_OUT = 7, CF_EVAL = 8 };
+
+// Arguments of the CF_INIT / CF_ACCEPT* / CF_EVAL tails, passed by value
+// to the producing kernel (unused by the tCG tails):
+//   CF_INIT        a = tol, b = Delta0, c = theta, d = kappa
+//   CF_ACCEPT      a = accept_rho
+//   CF_ACCEPT_OUT  a = accept_rho, dst = mapped host copy of the control
+//                  block, fence = the solve's OUT fence
+//   CF_EVAL        dst = the three evaluation scalars, fence = the
+//                  evaluation's OUT fence (nullptr: none to release)
+struct TailArgs {
+  double a = 0.0, b = 0.0, c = 0.0, d = 0.0;
+  double* dst = nullptr;
+  unsigned int* fence = nullptr;
+};
 
 // after z0 projection+dot (C_DOT0 = <z0, r0>)
 __device__ void ctrl_tail_z0(double* ctrl) {
@@ -223,14 +240,164 @@ __device__ void ctrl_tail_beta(double* ctrl) {
   ctrl_store(ctrl + C_ITER, ctrl[C_ITER] + 1.0);
 }
 
-__device__ __forceinline__ void run_ctrl_tail(int cf, double* ctrl) {
+// Solve head, after the gradient kernel: C_DOT0 = <QX + G, X>,
+// C_DOT1 = ||grad||^2, C_DOT2 = <G, X>
+//   => f = 0.5 <QX, X> + <G, X> = 0.5 (C_DOT0 + C_DOT2)
+// The body of k_ctrl_init and of the CF_INIT tail.
+__device__ void ctrl_body_init(double* ctrl, double tol, double Delta0,
+                               double theta, double kappa) {
+  const double fX = 0.5 * (ctrl_load(ctrl + C_DOT0)
+                           + ctrl_load(ctrl + C_DOT2));
+  const double gn0sq = ctrl_load(ctrl + C_DOT1);
+  ctrl_store(ctrl + C_FX, fX);
+  ctrl_store(ctrl + C_GN0SQ, gn0sq);
+  ctrl_store(ctrl + C_RR, gn0sq);
+  const double norm_r0 = sqrt(gn0sq);
+  ctrl_store(ctrl + C_BOUND, norm_r0 * fmin(pow(norm_r0, theta), kappa));
+  ctrl_store(ctrl + C_RADIUS, Delta0);
+  ctrl_store(ctrl + C_EPE, 0.0);
+  ctrl_store(ctrl + C_EPD, 0.0);
+  ctrl_store(ctrl + C_ITER, 0.0);
+  ctrl_store(ctrl + C_J, 0.0);
+  ctrl_store(ctrl + C_USE_CURRENT, 0.0);
+  ctrl_store(ctrl + C_STOP_PENDING, 0.0);
+  ctrl_store(ctrl + C_BETA, 0.0);
+  ctrl_store(ctrl + C_STATUS,
+             (norm_r0 < tol) ? (double)ST_NO_UPDATE : (double)ST_RUN);
+  ctrl_store(ctrl + C_DOT0, 0.0);
+  ctrl_store(ctrl + C_DOT1, 0.0);
+  ctrl_store(ctrl + C_DOT2, 0.0);
+  ctrl_store(ctrl + C_DOT3, 0.0);
+}
+
+// Candidate selection for the current radius: replay the stored Krylov
+// scalars, find the truncation point and the model decrease. The replay
+// only reads (C_RADIUS, C_HLEN, the history); ctrl_candidate_store
+// writes the result. The body of k_ctrl_candidate and of k_candidate.
+struct CandSel {
+  int jstar;  // < 0: full step (no truncation at this radius)
+  double taustar, dm;
+};
+
+__device__ CandSel ctrl_candidate_replay(const double* ctrl) {
+  const double radius = ctrl[C_RADIUS];
+  const int hlen = (int)ctrl[C_HLEN];
+  CandSel sel;
+  sel.dm = 0.0;
+  sel.jstar = -1;
+  sel.taustar = 0.0;
+  for (int j = 0; j < hlen && j < MAX_TCG; ++j) {
+    const double z_r = ctrl[H_ZR(j)];
+    const double d_Hd = ctrl[H_DHD(j)];
+    const double e_Pe = ctrl[H_EPE(j)];
+    const double e_Pd = ctrl[H_EPD(j)];
+    const double d_Pd = ctrl[H_DPD(j)];
+    const double alpha = z_r / d_Hd;
+    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
+    if (d_Hd <= 0.0 || e_Pe_new >= radius * radius) {
+      const double disc = e_Pd * e_Pd + d_Pd * (radius * radius - e_Pe);
+      const double tau = (d_Pd > 0.0)
+          ? (-e_Pd + sqrt(fmax(disc, 0.0))) / d_Pd : 0.0;
+      sel.dm += tau * z_r - 0.5 * tau * tau * d_Hd;
+      sel.jstar = j;
+      sel.taustar = tau;
+      break;
+    }
+    sel.dm += 0.5 * alpha * z_r;
+  }
+  return sel;
+}
+
+__device__ void ctrl_candidate_store(double* ctrl, const CandSel& sel) {
+  if (sel.jstar < 0) {
+    ctrl[C_USE_CURRENT] = 1.0;
+  } else {
+    ctrl[C_USE_CURRENT] = 0.0;
+    ctrl[C_JSTAR] = (double)sel.jstar;
+    ctrl[C_TAUSTAR] = sel.taustar;
+  }
+  ctrl[C_DM] = sel.dm;
+  ctrl[C_DOT0] = 0.0;
+  ctrl[C_DOT2] = 0.0;
+}
+
+// Acceptance test after the f(X_prop) dots (C_DOT0 = <QXp, Xp>,
+// C_DOT2 = <G, Xp>). The body of k_ctrl_accept and of the CF_ACCEPT*
+// tails.
+__device__ void ctrl_body_accept(double* ctrl, double accept_rho) {
+  if (ctrl[C_STATUS] != (double)ST_TCG_STOP) return;
+  const double fprop = 0.5 * ctrl_load(ctrl + C_DOT0)
+                       + ctrl_load(ctrl + C_DOT2);
+  ctrl_store(ctrl + C_DOT0, 0.0);
+  ctrl_store(ctrl + C_DOT2, 0.0);
+  ctrl_store(ctrl + C_FPROP, fprop);
+  const double fX = ctrl[C_FX];
+  const double dm = ctrl[C_DM];
+  const double rho = (fX - fprop) / fmax(dm, 1e-300);
+  ctrl_store(ctrl + C_RHO, rho);
+  if (rho > accept_rho && fprop <= fX) {
+    ctrl_store(ctrl + C_STATUS, (double)ST_ACCEPTED);
+  }
+}
+
+// Per-round evaluation, after its gradient kernel: dst[0..2] =
+// [f, 0.5 <X, G>, gradnorm^2] from C_DOT0 = <QX + G, X>, C_DOT2 = <G, X>,
+// C_DOT1 = ||P_X(QX + G)||^2. The dot slots are then cleaned for the
+// next evaluation (solves re-zero the whole control block themselves;
+// the ctx allocation is zero-initialized, so "dot slots are zero on eval
+// entry" holds from the start). The body of k_eval_combine and of the
+// CF_EVAL tail; the stores to dst are agent-scope because
+// k_gather3_fenced reads them from another stream.
+__device__ void ctrl_body_eval(double* ctrl, double* dst) {
+  const double d0 = ctrl_load(ctrl + C_DOT0);
+  const double d1 = ctrl_load(ctrl + C_DOT1);
+  const double d2 = ctrl_load(ctrl + C_DOT2);
+  ctrl_store(dst + 0, 0.5 * (d0 + d2));  // f(X)
+  ctrl_store(dst + 1, 0.5 * d2);         // 0.5 <X, G>
+  ctrl_store(dst + 2, d1);               // gradnorm^2
+  ctrl_store(ctrl + C_DOT0, 0.0);
+  ctrl_store(ctrl + C_DOT1, 0.0);
+  ctrl_store(ctrl + C_DOT2, 0.0);
+  ctrl_store(ctrl + C_DOT3, 0.0);
+}
+
+__device__ __forceinline__ void run_ctrl_tail(int cf, double* ctrl,
+                                              const TailArgs& ta) {
   switch (cf) {
     case CF_Z0: ctrl_tail_z0(ctrl); break;
     case CF_ALPHA: ctrl_tail_alpha(ctrl); break;
     case CF_RR: ctrl_tail_rr(ctrl); break;
     case CF_BETA: ctrl_tail_beta(ctrl); break;
+    case CF_INIT: ctrl_body_init(ctrl, ta.a, ta.b, ta.c, ta.d); break;
+    case CF_ACCEPT:
+    case CF_ACCEPT_OUT: ctrl_body_accept(ctrl, ta.a); break;
+    case CF_EVAL:
+      ctrl_body_eval(ctrl, ta.dst);
+      // the release orders the scalars in front of the fence
+      if (ta.fence)
+        __hip_atomic_store(ta.fence, 1u, __ATOMIC_RELEASE,
+                           __HIP_MEMORY_SCOPE_AGENT);
+      break;
     default: break;
   }
+}
+
+// End of a solve sequence, run by one whole block: copy the control
+// block to the mapped host buffer, then release the solve's OUT fence.
+// The system-scope fence puts every lane's host stores in front of the
+// release. What k_ctrl_to_host + k_fence_signal do in two launches.
+__device__ __forceinline__ void ctrl_publish(double* ctrl,
+                                             const TailArgs& ta) {
+  // thread 0 may just have run a tail: its stores reach L2 first
+  if (threadIdx.x == 0) __threadfence();
+  __syncthreads();
+  for (int i = threadIdx.x; i < CTRL_SIZE; i += blockDim.x)
+    ta.dst[i] = ctrl_load(ctrl + i);
+  __threadfence_system();
+  __syncthreads();
+  if (threadIdx.x == 0)
+    __hip_atomic_store(ta.fence, 1u, __ATOMIC_RELEASE,
+                       __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // wave-level + block-level reduction, then one atomicAdd per block
@@ -265,12 +432,16 @@ __device__ __forceinline__ void finish_reduction(double* ctrl,
                                                  int slot1 = -1,
                                                  double d1 = 0.0,
                                                  int slot2 = -1,
-                                                 double d2 = 0.0) {
+                                                 double d2 = 0.0,
+                                                 const TailArgs& ta =
+                                                     TailArgs()) {
   if (slot0 >= 0) block_reduce_atomic(d0, ctrl + slot0);
   if (slot1 >= 0) block_reduce_atomic(d1, ctrl + slot1);
   if (slot2 >= 0) block_reduce_atomic(d2, ctrl + slot2);
   if (CF != CF_NONE) {
-    if (fanin_last_block(ctrl) && threadIdx.x == 0) run_ctrl_tail(CF, ctrl);
+    const bool last = fanin_last_block(ctrl);
+    if (last && threadIdx.x == 0) run_ctrl_tail(CF, ctrl, ta);
+    if (CF == CF_ACCEPT_OUT && last) ctrl_publish(ctrl, ta);
   }
 }
 
@@ -641,6 +812,15 @@ __global__ void k_proj_wide(const double* __restrict__ X,
 // gradient launch: a second copy of the result in out2, and zero_out's
 // rows of this pose cleared. A template parameter, so that the tCG-loop
 // instantiations keep their register budget.
+// AUX = 2 (MODE 0 only) is the tCG Hd stage with the direction update
+// folded in: the direction delta = beta * delta_old - z is not read from
+// memory but formed per neighbour as fma(beta, delta_old[j], -z[j]), the
+// single fma of k_tcg_delta, so the bits are the same. delta is double
+// buffered (zero_out = buffer 0, out2 = buffer 1, dotW = z; V is not
+// used): iteration C_ITER
+// writes its own pose's tile into buffer C_ITER & 1 and reads the other,
+// so no block reads what another writes, and the choice travels with the
+// control block across the continuation graph.
 template <int D, int R, int MODE, int CF = CF_NONE, int AUX = 0>
 __global__ void k_hess_fused(const int* __restrict__ row_ptr,
                              const int* __restrict__ col_idx,
@@ -654,12 +834,27 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
                              int n, int dot_slot, int dot_slot2,
                              int dot_slot3, int guard,
                              double* __restrict__ out2,
-                             double* __restrict__ zero_out) {
-  if (guarded_off(ctrl, guard)) return;
+                             double* __restrict__ zero_out, TailArgs ta) {
+  if (guarded_off(ctrl, guard)) {
+    // the CF_ACCEPT_OUT publish step is unguarded, like the two launches
+    // it replaces: the host reads the control block whatever the status
+    if (CF == CF_ACCEPT_OUT && blockIdx.x == 0) ctrl_publish(ctrl, ta);
+    return;
+  }
   constexpr int dh = D + 1;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   double acc[dh][R];
   double d0 = 0.0, d1 = 0.0, d2 = 0.0;
+  // AUX == 2: old / new direction buffer by the parity of C_ITER
+  const double* dold = nullptr;
+  double* dnew = nullptr;
+  double beta = 0.0;
+  if (AUX == 2) {
+    const bool odd = ((int)ctrl[C_ITER]) & 1;
+    dold = odd ? zero_out : out2;
+    dnew = odd ? out2 : zero_out;
+    beta = ctrl[C_BETA];
+  }
   if (i < n) {
     #pragma unroll
     for (int c = 0; c < dh; ++c)
@@ -668,7 +863,29 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
     const int s0 = row_ptr[i], e0 = row_ptr[i + 1];
     for (int p = s0; p < e0; ++p) {
       const double* B = vals + (size_t)p * dh * dh;
-      const double* Vj = V + (size_t)col_idx[p] * dh * R;
+      const size_t jo = (size_t)col_idx[p] * dh * R;
+      if (AUX == 2) {
+        // one row of the neighbour's direction at a time (R values live
+        // instead of the tile); every acc[c][k] still adds its cc terms
+        // in the order 0 .. dh-1, as below
+        #pragma unroll
+        for (int cc = 0; cc < dh; ++cc) {
+          double v[R];
+          #pragma unroll
+          for (int k = 0; k < R; ++k)
+            v[k] = fma(beta, dold[jo + cc * R + k], -dotW[jo + cc * R + k]);
+          #pragma unroll
+          for (int c = 0; c < dh; ++c) {
+            const double b = B[c * dh + cc];
+            #pragma unroll
+            for (int k = 0; k < R; ++k) acc[c][k] = fma(b, v[k], acc[c][k]);
+          }
+          // keep the next rows' loads from being hoisted over this one
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        continue;
+      }
+      const double* Vj = V + jo;
       #pragma unroll
       for (int c = 0; c < dh; ++c)
         #pragma unroll
@@ -715,21 +932,36 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
       }
       tangent_project<D, R>(Xi, acc);
       double* Oi = out + (size_t)i * dh * R;
-      double* O2 = (AUX && out2) ? out2 + (size_t)i * dh * R : nullptr;
+      double* O2 = (AUX == 1 && out2) ? out2 + (size_t)i * dh * R : nullptr;
       const double* Wi = dotW ? dotW + (size_t)i * dh * R : nullptr;
       #pragma unroll
       for (int c = 0; c < dh; ++c)
         #pragma unroll
         for (int k = 0; k < R; ++k) {
           Oi[c * R + k] = acc[c][k];
-          if (AUX && O2) O2[c * R + k] = acc[c][k];
-          if (dot_slot >= 0) {
+          if (AUX == 1 && O2) O2[c * R + k] = acc[c][k];
+          if (AUX != 2 && dot_slot >= 0) {
             const double w = Wi ? Wi[c * R + k] : acc[c][k];
             d0 = fma(acc[c][k], w, d0);
           }
         }
+      if (AUX == 2) {
+        // this pose's tile of the new direction and <delta, Hd>, in a
+        // pass of its own behind the projection so that its loads are
+        // not live across it; same element order as the loop above
+        __builtin_amdgcn_sched_barrier(0);
+        #pragma unroll
+        for (int c = 0; c < dh; ++c)
+          #pragma unroll
+          for (int k = 0; k < R; ++k) {
+            const size_t e = (size_t)i * dh * R + c * R + k;
+            const double w = fma(beta, dold[e], -dotW[e]);
+            dnew[e] = w;
+            d0 = fma(acc[c][k], w, d0);
+          }
+      }
       // the next j-split dense apply accumulates into this buffer
-      if (AUX && zero_out) {
+      if (AUX == 1 && zero_out) {
         double* Zi = zero_out + (size_t)i * dh * R;
         #pragma unroll
         for (int e = 0; e < dh * R; ++e) Zi[e] = 0.0;
@@ -737,7 +969,7 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
     }
   }
   finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1,
-                       MODE == 0 ? dot_slot3 : -1, d2);
+                       MODE == 0 ? dot_slot3 : -1, d2, ta);
 }
 
 // ---------------------------------------------------------------------
@@ -763,8 +995,13 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
                             int n, int dot_slot, int dot_slot2,
                             int dot_slot3, int guard,
                             double* __restrict__ out2,
-                            double* __restrict__ zero_out) {
-  if (guarded_off(ctrl, guard)) return;
+                            double* __restrict__ zero_out, TailArgs ta) {
+  if (guarded_off(ctrl, guard)) {
+    // the CF_ACCEPT_OUT publish step is unguarded, like the two launches
+    // it replaces: the host reads the control block whatever the status
+    if (CF == CF_ACCEPT_OUT && blockIdx.x == 0) ctrl_publish(ctrl, ta);
+    return;
+  }
   constexpr int dh = D + 1;
   constexpr int TILE = dh * R;
   constexpr int PB = 256 / TILE;  // poses per block
@@ -821,7 +1058,7 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
     __syncthreads();  // sAcc/sX reuse barrier for CF tail safety
   }
   finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1,
-                       MODE == 0 ? dot_slot3 : -1, d2);
+                       MODE == 0 ? dot_slot3 : -1, d2, ta);
 }
 
 // ---------------------------------------------------------------------
@@ -959,6 +1196,37 @@ __device__ __forceinline__ void spd_inv_sqrt(const double S[D][D],
     for (int j = 0; j < D; ++j) out[i][j] = Z[i][j] * c;
 }
 
+// Oi = one pose's polar projection of the register tile Mt: polar of its
+// D Stiefel rows, the translation row unchanged.
+template <int D, int R>
+__device__ __forceinline__ void polar_tile(const double (&Mt)[D + 1][R],
+                                           double* Oi) {
+  // Gram = Mt Mt^T (D x D); polar(Mt) = Gram^{-1/2} Mt
+  double S[D][D];
+  #pragma unroll
+  for (int a = 0; a < D; ++a)
+    #pragma unroll
+    for (int b = 0; b < D; ++b) {
+      double s = 0.0;
+      #pragma unroll
+      for (int k = 0; k < R; ++k) s = fma(Mt[a][k], Mt[b][k], s);
+      S[a][b] = s;
+    }
+  double Gi[D][D];
+  spd_inv_sqrt<D>(S, Gi);
+  #pragma unroll
+  for (int a = 0; a < D; ++a)
+    #pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double s = 0.0;
+      #pragma unroll
+      for (int b = 0; b < D; ++b) s = fma(Gi[a][b], Mt[b][k], s);
+      Oi[a * R + k] = s;
+    }
+  #pragma unroll
+  for (int k = 0; k < R; ++k) Oi[D * R + k] = Mt[D][k];
+}
+
 template <int D, int R>
 __global__ void k_polar_affine(const double* __restrict__ A,
                                const double* __restrict__ B,
@@ -984,31 +1252,7 @@ __global__ void k_polar_affine(const double* __restrict__ A,
       if (Ci) v = fma(cc, Ci[c * R + k], v);
       Mt[c][k] = v;
     }
-  // Gram = Mt Mt^T (D x D); polar(Mt) = Gram^{-1/2} Mt
-  double S[D][D];
-  #pragma unroll
-  for (int a = 0; a < D; ++a)
-    #pragma unroll
-    for (int b = 0; b < D; ++b) {
-      double s = 0.0;
-      #pragma unroll
-      for (int k = 0; k < R; ++k) s = fma(Mt[a][k], Mt[b][k], s);
-      S[a][b] = s;
-    }
-  double Gi[D][D];
-  spd_inv_sqrt<D>(S, Gi);
-  double* Oi = out + (size_t)i * dh * R;
-  #pragma unroll
-  for (int a = 0; a < D; ++a)
-    #pragma unroll
-    for (int k = 0; k < R; ++k) {
-      double s = 0.0;
-      #pragma unroll
-      for (int b = 0; b < D; ++b) s = fma(Gi[a][b], Mt[b][k], s);
-      Oi[a * R + k] = s;
-    }
-  #pragma unroll
-  for (int k = 0; k < R; ++k) Oi[D * R + k] = Mt[D][k];
+  polar_tile<D, R>(Mt, out + (size_t)i * dh * R);
 }
 
 // ---------------------------------------------------------------------
@@ -1045,11 +1289,28 @@ __global__ void k_precond_dense(const float* __restrict__ Minv,
       shv[t] = V[(size_t)(j0 + t / R) * R + (t % R)];
     __syncthreads();
     if (i < N) {
-      for (int j = 0; j < jn; ++j) {
-        const double m = (double)Minv[(size_t)(j0 + j) * N + i];
+      // eight independent 4-byte loads in flight per lane before the
+      // first is consumed (one dependent load per j left the kernel at
+      // ~0.55 TB/s); the fma order over j is unchanged
+      const float* Mc = Minv + (size_t)j0 * N + i;
+      int j = 0;
+      for (; j + 8 <= jn; j += 8) {
+        float m[8];
+        #pragma unroll
+        for (int u = 0; u < 8; ++u) m[u] = Mc[(size_t)(j + u) * N];
+        #pragma unroll
+        for (int u = 0; u < 8; ++u) {
+          const double md = (double)m[u];
+          #pragma unroll
+          for (int k = 0; k < R; ++k)
+            acc[k] = fma(md, shv[(j + u) * R + k], acc[k]);
+        }
+      }
+      for (; j < jn; ++j) {
+        const double md = (double)Mc[(size_t)j * N];
         #pragma unroll
         for (int k = 0; k < R; ++k)
-          acc[k] = fma(m, shv[j * R + k], acc[k]);
+          acc[k] = fma(md, shv[j * R + k], acc[k]);
       }
     }
   }
@@ -1096,18 +1357,22 @@ __global__ void k_precond_jacobi(const double* __restrict__ L,
 template <int CF = CF_NONE>
 __global__ void k_tcg_update(double* __restrict__ eta,
                              double* __restrict__ rvec,
-                             const double* __restrict__ delta,
+                             const double* __restrict__ delta0,
                              const double* __restrict__ Hd,
                              double* __restrict__ eta_snap,
                              double* __restrict__ delta_snap,
                              double* __restrict__ ctrl,
                              long total,
-                             double* __restrict__ zero_out) {
+                             double* __restrict__ zero_out,
+                             const double* __restrict__ delta1) {
   if (guarded_off(ctrl, ST_RUN)) return;
   const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const double coef = ctrl[C_COEF];
   const int stop_pending = (int)ctrl[C_STOP_PENDING];
   const int j = (int)ctrl[C_ITER];
+  // double-buffered direction (delta1 != nullptr): iteration j's lives
+  // in buffer j & 1, where the Hd stage in front wrote it
+  const double* delta = (delta1 && (j & 1)) ? delta1 : delta0;
   double rr = 0.0;
   #pragma unroll
   for (int u = 0; u < 4; ++u) {
@@ -1166,6 +1431,55 @@ __global__ void k_form_step(double* __restrict__ step,
   }
 }
 
+// One trust-region candidate in one launch: k_ctrl_candidate, k_form_step
+// and k_polar_affine(X, step, 1, 1) back to back, one thread per pose.
+// Thread 0 of every block replays the (at most MAX_TCG entries of)
+// Krylov history for itself and hands the selection to its block through
+// LDS; the replay reads only slots that this kernel does not write, and
+// block 0 alone stores the selection, so no block can see another's
+// store. Each thread forms its pose's step tile in registers (the same
+// single fma per element as k_form_step), stores it, and retracts
+// X + step into Xprop.
+template <int D, int R>
+__global__ void k_candidate(double* __restrict__ ctrl,
+                            double* __restrict__ step,
+                            const double* __restrict__ eta,
+                            const double* __restrict__ eta_snap,
+                            const double* __restrict__ delta_snap,
+                            const double* __restrict__ X,
+                            double* __restrict__ Xprop, int n) {
+  if (guarded_off(ctrl, ST_TCG_STOP)) return;
+  __shared__ CandSel sel_sh;
+  if (threadIdx.x == 0) {
+    sel_sh = ctrl_candidate_replay(ctrl);
+    if (blockIdx.x == 0) ctrl_candidate_store(ctrl, sel_sh);
+  }
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr int dh = D + 1;
+  const int jstar = sel_sh.jstar;
+  const double tau = sel_sh.taustar;
+  const size_t total = (size_t)n * dh * R;
+  const size_t base = (size_t)i * dh * R;
+  const double* Ei = (jstar < 0 ? eta : eta_snap + (size_t)jstar * total)
+                     + base;
+  const double* Di = delta_snap + (size_t)(jstar < 0 ? 0 : jstar) * total
+                     + base;
+  double Mt[dh][R];
+  #pragma unroll
+  for (int c = 0; c < dh; ++c)
+    #pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double st = Ei[c * R + k];
+      if (jstar >= 0) st = fma(tau, Di[c * R + k], st);
+      step[base + c * R + k] = st;
+      // k_polar_affine's 1 * X, then fma(1, step, .)
+      Mt[c][k] = fma(1.0, st, X[base + c * R + k]);
+    }
+  polar_tile<D, R>(Mt, Xprop + base);
+}
+
 // out = a*A + b*B elementwise (unguarded helper)
 __global__ void k_axpby(const double* __restrict__ A,
                         const double* __restrict__ B,
@@ -1201,29 +1515,7 @@ __global__ void k_dots(const double* __restrict__ A,
 // ---------------------------------------------------------------------
 __global__ void k_ctrl_init(double* ctrl, double tol, double Delta0,
                             double theta, double kappa) {
-  if (threadIdx.x != 0) return;
-  // C_DOT0 = <QX + G, X>, C_DOT2 = <G, X>
-  // => f = 0.5 <QX, X> + <G, X> = 0.5 (C_DOT0 + C_DOT2)
-  const double fX = 0.5 * (ctrl[C_DOT0] + ctrl[C_DOT2]);
-  const double gn0sq = ctrl[C_DOT1];
-  ctrl[C_FX] = fX;
-  ctrl[C_GN0SQ] = gn0sq;
-  ctrl[C_RR] = gn0sq;
-  const double norm_r0 = sqrt(gn0sq);
-  ctrl[C_BOUND] = norm_r0 * fmin(pow(norm_r0, theta), kappa);
-  ctrl[C_RADIUS] = Delta0;
-  ctrl[C_EPE] = 0.0;
-  ctrl[C_EPD] = 0.0;
-  ctrl[C_ITER] = 0.0;
-  ctrl[C_J] = 0.0;
-  ctrl[C_USE_CURRENT] = 0.0;
-  ctrl[C_STOP_PENDING] = 0.0;
-  ctrl[C_BETA] = 0.0;
-  ctrl[C_STATUS] = (norm_r0 < tol) ? (double)ST_NO_UPDATE : (double)ST_RUN;
-  ctrl[C_DOT0] = 0.0;
-  ctrl[C_DOT1] = 0.0;
-  ctrl[C_DOT2] = 0.0;
-  ctrl[C_DOT3] = 0.0;
+  if (threadIdx.x == 0) ctrl_body_init(ctrl, tol, Delta0, theta, kappa);
 }
 
 // Standalone launch of one control tail (ctrl_tail_z0/alpha/rr/beta):
@@ -1231,7 +1523,7 @@ __global__ void k_ctrl_init(double* ctrl, double tol, double Delta0,
 // the tail fused into that kernel's last block.
 template <int CF>
 __global__ void k_ctrl_tail(double* ctrl) {
-  if (threadIdx.x == 0) run_ctrl_tail(CF, ctrl);
+  if (threadIdx.x == 0) run_ctrl_tail(CF, ctrl, TailArgs());
 }
 
 template <int CF>
@@ -1254,58 +1546,12 @@ __global__ void k_ctrl_tcg_end(double* ctrl) {
 __global__ void k_ctrl_candidate(double* ctrl) {
   if (threadIdx.x != 0) return;
   if (ctrl[C_STATUS] != (double)ST_TCG_STOP) return;
-  const double radius = ctrl[C_RADIUS];
-  const int hlen = (int)ctrl[C_HLEN];
-  double dm = 0.0;
-  int jstar = -1;
-  double taustar = 0.0;
-  for (int j = 0; j < hlen && j < MAX_TCG; ++j) {
-    const double z_r = ctrl[H_ZR(j)];
-    const double d_Hd = ctrl[H_DHD(j)];
-    const double e_Pe = ctrl[H_EPE(j)];
-    const double e_Pd = ctrl[H_EPD(j)];
-    const double d_Pd = ctrl[H_DPD(j)];
-    const double alpha = z_r / d_Hd;
-    const double e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
-    if (d_Hd <= 0.0 || e_Pe_new >= radius * radius) {
-      const double disc = e_Pd * e_Pd + d_Pd * (radius * radius - e_Pe);
-      const double tau = (d_Pd > 0.0)
-          ? (-e_Pd + sqrt(fmax(disc, 0.0))) / d_Pd : 0.0;
-      dm += tau * z_r - 0.5 * tau * tau * d_Hd;
-      jstar = j;
-      taustar = tau;
-      break;
-    }
-    dm += 0.5 * alpha * z_r;
-  }
-  if (jstar < 0) {
-    // full step (no truncation at this radius)
-    ctrl[C_USE_CURRENT] = 1.0;
-  } else {
-    ctrl[C_USE_CURRENT] = 0.0;
-    ctrl[C_JSTAR] = (double)jstar;
-    ctrl[C_TAUSTAR] = taustar;
-  }
-  ctrl[C_DM] = dm;
-  ctrl[C_DOT0] = 0.0;
-  ctrl[C_DOT2] = 0.0;
+  ctrl_candidate_store(ctrl, ctrl_candidate_replay(ctrl));
 }
 
 // acceptance test after f(X_prop) dots (C_DOT0 = <QXp, Xp>, C_DOT2 = <G, Xp>)
 __global__ void k_ctrl_accept(double* ctrl, double accept_rho) {
-  if (threadIdx.x != 0) return;
-  if (ctrl[C_STATUS] != (double)ST_TCG_STOP) return;
-  const double fprop = 0.5 * ctrl[C_DOT0] + ctrl[C_DOT2];
-  ctrl[C_DOT0] = 0.0;
-  ctrl[C_DOT2] = 0.0;
-  ctrl[C_FPROP] = fprop;
-  const double fX = ctrl[C_FX];
-  const double dm = ctrl[C_DM];
-  const double rho = (fX - fprop) / fmax(dm, 1e-300);
-  ctrl[C_RHO] = rho;
-  if (rho > accept_rho && fprop <= fX) {
-    ctrl[C_STATUS] = (double)ST_ACCEPTED;
-  }
+  if (threadIdx.x == 0) ctrl_body_accept(ctrl, accept_rho);
 }
 
 // shrink the radius after a rejection (host re-enqueues the candidate set)
@@ -1535,23 +1781,26 @@ static void launch_hess_fused(const int* rp, const int* ci,
                               int dot_slot, int dot_slot2, int guard,
                               hipStream_t s, int dot_slot3 = -1,
                               double* out2 = nullptr,
-                              double* zero_out = nullptr) {
-  const bool wide = hess_use_wide(n);
+                              double* zero_out = nullptr,
+                              const TailArgs& ta = TailArgs()) {
+  // AUX == 2 (folded direction) exists for the thread-per-pose kernel
+  // only; its callers do not fold when the wide kernels are selected
+  const bool wide = AUX != 2 && hess_use_wide(n);
   if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
         constexpr int D = Dc, R = Rc;
         if (wide) {
           constexpr int PB = 256 / ((D + 1) * R);
-          hipLaunchKernelGGL((k_hess_wide<D, R, MODE, CF, AUX>),
+          hipLaunchKernelGGL((k_hess_wide<D, R, MODE, CF, AUX == 2 ? 0 : AUX>),
                              dim3(blocks_for(n, PB)), dim3(256), 0, s,
                              rp, ci, vals, V, X, G, out, dotW, ctrl, n,
                              dot_slot, dot_slot2, dot_slot3, guard, out2,
-                             zero_out);
+                             zero_out, ta);
         } else {
           hipLaunchKernelGGL((k_hess_fused<D, R, MODE, CF, AUX>),
                              dim3(blocks_for(n, 256)), dim3(256), 0, s,
                              rp, ci, vals, V, X, G, out, dotW, ctrl, n,
                              dot_slot, dot_slot2, dot_slot3, guard, out2,
-                             zero_out);
+                             zero_out, ta);
         }
       }))
     dpo_bad_shape(d, r);
@@ -1566,10 +1815,16 @@ __global__ void k_dzero(double* p, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0.0;
 }
+// two buffers in one launch (the solve head's G_buf and control block)
+__global__ void k_dzero2(double* p, long n, double* q, long m) {
+  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) p[i] = 0.0;
+  if (i < m) q[i] = 0.0;
+}
 __global__ void k_ctrl_to_host(const double* __restrict__ src,
                                double* __restrict__ dst, int n) {
-  int i = threadIdx.x;
-  if (i < n) dst[i] = src[i];
+  // one wave copies all n slots (n = CTRL_SIZE exceeds the wave)
+  for (int i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
 }
 
 static inline void dzero(double* p, long n, hipStream_t s) {
@@ -1623,11 +1878,12 @@ template <int CF>
 static void launch_tcg_update(double* eta, double* rvec, const double* delta,
                               const double* Hd, double* eta_snap,
                               double* delta_snap, double* ctrl, long total,
-                              double* zero_out, hipStream_t s) {
+                              double* zero_out, hipStream_t s,
+                              const double* delta1 = nullptr) {
   hipLaunchKernelGGL((k_tcg_update<CF>),
                      dim3(blocks_for((total + 3) / 4, 256)), dim3(256), 0, s,
                      eta, rvec, delta, Hd, eta_snap, delta_snap, ctrl, total,
-                     zero_out);
+                     zero_out, delta1);
 }
 
 extern "C" {
@@ -1805,21 +2061,7 @@ void dpo_gnc_weights(const double* X, const double* nbr, const long* e1_idx,
 // combine kernel: out[0..2] = [f, 0.5<X,G>, gn2] from dot slots
 __global__ void k_eval_combine(double* __restrict__ ctrl,
                                double* __restrict__ out) {
-  if (threadIdx.x != 0) return;
-  // C_DOT0 = <QX + G, X>, C_DOT2 = <G, X>, C_DOT1 = ||P_X(QX+G)||^2
-  out[0] = 0.5 * (ctrl[C_DOT0] + ctrl[C_DOT2]);   // f(X)
-  out[1] = 0.5 * ctrl[C_DOT2];                    // 0.5 <X, G>
-  out[2] = ctrl[C_DOT1];                          // gradnorm^2
-  // self-clean the dot slots for the next eval: saves the standalone
-  // 32-byte dzero launch per evaluation (12.8% of bench-scale kernel
-  // launches were k_dzero calls, profiles/bench_r2_kernel_stats.csv).
-  // Solves re-zero the whole control block themselves; the ctx
-  // allocation is zero-initialized, so the invariant "dot slots are
-  // zero on eval entry" holds from the start.
-  ctrl[C_DOT0] = 0.0;
-  ctrl[C_DOT1] = 0.0;
-  ctrl[C_DOT2] = 0.0;
-  ctrl[C_DOT3] = 0.0;
+  if (threadIdx.x == 0) ctrl_body_eval(ctrl, out);
 }
 
 // One cached hipGraph exec for a fixed-pointer enqueue sequence.
@@ -1893,7 +2135,7 @@ static bool graph_cache_launch(GraphCache& g, const void* const (&key)[4],
 struct DpoCtx {
   int n, d, r, dh, N, max_inner;
   long total;
-  double *W, *grad, *eta, *delta, *rvec, *z, *Hd, *step, *Xprop;
+  double *W, *grad, *eta, *delta, *delta1, *rvec, *z, *Hd, *step, *Xprop;
   double *eta_snap, *delta_snap, *ctrl;
   double *ctrl_host;      // pinned
   double *ctrl_host_dev;  // device-side view of ctrl_host (mapped)
@@ -1994,9 +2236,22 @@ static inline void fence_wait(DpoCtx* c, int which, hipStream_t s) {
                      c->fences + which);
 }
 
-static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s) {
-  if (c->g_ne == 0) { c->Gt = nullptr; return; }
-  dzero(c->G_buf, c->total, s);
+// with_ctrl: the launch that clears G_buf clears the control block too
+// (solve head).
+static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s,
+                           bool with_ctrl = false) {
+  if (c->g_ne == 0) {
+    c->Gt = nullptr;
+    if (with_ctrl) dzero(c->ctrl, CTRL_SIZE, s);
+    return;
+  }
+  if (with_ctrl) {
+    const long m = c->total > CTRL_SIZE ? c->total : CTRL_SIZE;
+    hipLaunchKernelGGL(k_dzero2, dim3(blocks_for(m, 256)), dim3(256), 0, s,
+                       c->G_buf, c->total, c->ctrl, (long)CTRL_SIZE);
+  } else {
+    dzero(c->G_buf, c->total, s);
+  }
   hipLaunchKernelGGL(k_g_assemble,
                      dim3(((long)c->g_ne * c->dh * c->r + 255) / 256),
                      dim3(256), 0, s, c->G_buf, c->g_E0, c->g_local_pose,
@@ -2030,11 +2285,12 @@ static void ctx_hess(DpoCtx* c, const double* V, const double* X,
                      const double* G, double* out, const double* dotW,
                      int dot_slot, int dot_slot2, int guard, hipStream_t s,
                      int dot_slot3 = -1, double* out2 = nullptr,
-                     double* zero_out = nullptr) {
+                     double* zero_out = nullptr,
+                     const TailArgs& ta = TailArgs()) {
   launch_hess_fused<MODE, CF, AUX>(c->q_rp, c->q_ci, c->q_vals, V, X, G, out,
                                    dotW, c->ctrl, c->n, c->d, c->r, dot_slot,
                                    dot_slot2, guard, s, dot_slot3, out2,
-                                   zero_out);
+                                   zero_out, ta);
 }
 
 extern "C" {
@@ -2049,6 +2305,7 @@ void* dpo_ctx_create(int n, int d, int r, int max_inner) {
   DPO_CHECK(hipMalloc(&c->grad, vb));
   DPO_CHECK(hipMalloc(&c->eta, vb));
   DPO_CHECK(hipMalloc(&c->delta, vb));
+  DPO_CHECK(hipMalloc(&c->delta1, vb));
   DPO_CHECK(hipMalloc(&c->rvec, vb));
   DPO_CHECK(hipMalloc(&c->z, vb));
   DPO_CHECK(hipMalloc(&c->Hd, vb));
@@ -2066,6 +2323,7 @@ void* dpo_ctx_create(int n, int d, int r, int max_inner) {
   // patterns in fresh allocations) out of the recurrence, and the
   // per-solve zeroing passes are dropped from the captured body
   DPO_CHECK(hipMemset(c->delta, 0, vb));
+  DPO_CHECK(hipMemset(c->delta1, 0, vb));  // the "old" buffer of iteration 0
   DPO_CHECK(hipMemset(c->eta, 0, vb));
   DPO_CHECK(hipHostMalloc(&c->ctrl_host, CTRL_SIZE * sizeof(double)));
   DPO_CHECK(hipHostGetDevicePointer((void**)&c->ctrl_host_dev,
@@ -2086,7 +2344,7 @@ void* dpo_ctx_create(int n, int d, int r, int max_inner) {
 
 void dpo_ctx_destroy(void* h) {
   DpoCtx* c = (DpoCtx*)h;
-  dpo_ignore(hipFree(c->W)); dpo_ignore(hipFree(c->grad)); dpo_ignore(hipFree(c->eta)); dpo_ignore(hipFree(c->delta));
+  dpo_ignore(hipFree(c->W)); dpo_ignore(hipFree(c->grad)); dpo_ignore(hipFree(c->eta)); dpo_ignore(hipFree(c->delta)); dpo_ignore(hipFree(c->delta1));
   dpo_ignore(hipFree(c->rvec)); dpo_ignore(hipFree(c->z)); dpo_ignore(hipFree(c->Hd)); dpo_ignore(hipFree(c->step));
   dpo_ignore(hipFree(c->Xprop)); dpo_ignore(hipFree(c->eta_snap)); dpo_ignore(hipFree(c->delta_snap));
   c->invalidate_graphs();
@@ -2168,7 +2426,45 @@ static void enqueue_with_tail(DpoCtx* c, hipStream_t s, Launch launch) {
 }
 
 // Hd stage: Hd = P_X(Q delta), <delta, Hd>, alpha / boundary decision.
+// Folded (default): the direction update delta = beta * delta - z rides
+// in the same kernel (AUX = 2, double-buffered delta). Otherwise
+// k_tcg_delta has run behind the z stage, in place on buffer 0.
+// Folded with the dense preconditioner only, the small launch-bound
+// agents (same split as DPO_TCG_SEG_DENSE): with block-Jacobi at 125k
+// poses per agent the kernel's doubled neighbour loads cost more than the
+// launch saves (1M-pose round 11.05 -> 11.62 ms, RESULTS.md).
+// The fusions of this file's newer tails (CF_INIT, k_candidate,
+// CF_ACCEPT*, CF_EVAL, the folded Hd stage) serve the small, launch-bound
+// agents, which are the ones that use the dense preconditioner (the same
+// split as DPO_TCG_SEG_DENSE). With block-Jacobi at 125k poses per agent
+// a launch is noise and the fan-in of ~500 blocks per tail is not: the
+// 1M-pose round was 0.7 to 1 % slower with them in nine of nine pairs
+// (RESULTS.md), so that path keeps the standalone launches.
+static bool ctx_fuse_scalar(const DpoCtx* c) {
+  return c->Minv && !solve_no_cf();
+}
+
+// The folded Hd stage on raw pointers (solve body and dpo_hd_stage).
+static void launch_hd_folded(const int* rp, const int* ci,
+                             const double* vals, double* d0, double* d1,
+                             const double* z, const double* X, double* Hd,
+                             double* ctrl, int n, int d, int r,
+                             hipStream_t s) {
+  launch_hess_fused<0, CF_ALPHA, 2>(rp, ci, vals, nullptr, X, nullptr, Hd, z,
+                                    ctrl, n, d, r, C_DOT0, -1, ST_RUN, s, -1,
+                                    d1, d0);
+}
+
+static bool ctx_fold_delta(const DpoCtx* c) {
+  return ctx_fuse_scalar(c) && !hess_use_wide(c->n);
+}
+
 static void enqueue_hd_stage(DpoCtx* c, const double* X, hipStream_t s) {
+  if (ctx_fold_delta(c)) {
+    launch_hd_folded(c->q_rp, c->q_ci, c->q_vals, c->delta, c->delta1, c->z,
+                     X, c->Hd, c->ctrl, c->n, c->d, c->r, s);
+    return;
+  }
   enqueue_with_tail<CF_ALPHA>(c, s, [&](auto cf) {
     ctx_hess<0, cf>(c, c->delta, X, nullptr, c->Hd, c->delta, C_DOT0, -1,
                     ST_RUN, s);
@@ -2181,7 +2477,8 @@ static void enqueue_update_stage(DpoCtx* c, hipStream_t s) {
   enqueue_with_tail<CF_RR>(c, s, [&](auto cf) {
     launch_tcg_update<cf>(c->eta, c->rvec, c->delta, c->Hd, c->eta_snap,
                           c->delta_snap, c->ctrl, c->total,
-                          ctx_prezero_z(c), s);
+                          ctx_prezero_z(c), s,
+                          ctx_fold_delta(c) ? c->delta1 : nullptr);
   });
 }
 
@@ -2212,20 +2509,32 @@ static void enqueue_z_stage(DpoCtx* c, const double* X, hipStream_t s) {
 static void enqueue_solve_head(DpoCtx* c, double* X, const double* nbr,
                                double tol, double Delta0, hipStream_t s) {
   fence_wait(c, F_SOLVE_IN, s);  // first node: block until inputs ready
-  if (nbr) ctx_assemble_g(c, nbr, s);
-  dzero(c->ctrl, CTRL_SIZE, s);
+  // fused (default): G_buf and the control block cleared by one launch,
+  // the control init run by the gradient kernel's last block
+  const bool fused = ctx_fuse_scalar(c);
+  if (nbr) ctx_assemble_g(c, nbr, s, /*with_ctrl=*/fused);
+  if (!nbr || !fused) dzero(c->ctrl, CTRL_SIZE, s);
 
   // gradient phase: one fused kernel computes Q@X + G, projects at X
   // and accumulates <P,P> / <QX+G,X> (was spmm + proj_dots — the
   // two-kernel split re-read the full iterate from HBM). It writes the
   // gradient to grad and to rvec (the tCG residual starts as the
   // gradient) and clears z for the z0 dense apply.
-  ctx_hess<0, CF_NONE, 1>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0,
-                          -1, s, c->Gt ? C_DOT2 : -1,  // <G,X> folded in
-                          c->rvec, ctx_prezero_z(c));
-  dpo_ctrl_init(c->ctrl, tol, Delta0, 1.0, 0.1, s);
+  if (fused) {
+    TailArgs ta;
+    ta.a = tol; ta.b = Delta0; ta.c = 1.0; ta.d = 0.1;
+    ctx_hess<0, CF_INIT, 1>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0,
+                            -1, s, c->Gt ? C_DOT2 : -1, c->rvec,
+                            ctx_prezero_z(c), ta);
+  } else {
+    ctx_hess<0, CF_NONE, 1>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1,
+                            C_DOT0, -1, s,
+                            c->Gt ? C_DOT2 : -1,  // <G,X> folded in
+                            c->rvec, ctx_prezero_z(c));
+    dpo_ctrl_init(c->ctrl, tol, Delta0, 1.0, 0.1, s);
+  }
   enqueue_z_stage<CF_Z0>(c, X, s);
-  dpo_tcg_delta(c->delta, c->z, c->ctrl, c->total, s);
+  if (!ctx_fold_delta(c)) dpo_tcg_delta(c->delta, c->z, c->ctrl, c->total, s);
 }
 
 // `count` tCG iterations. Position-independent: every kernel reads the
@@ -2237,23 +2546,61 @@ static void enqueue_tcg_iters(DpoCtx* c, double* X, int count,
     enqueue_hd_stage(c, X, s);
     enqueue_update_stage(c, s);
     enqueue_z_stage<CF_BETA>(c, X, s);
-    dpo_tcg_delta(c->delta, c->z, c->ctrl, c->total, s);
+    if (!ctx_fold_delta(c))
+      dpo_tcg_delta(c->delta, c->z, c->ctrl, c->total, s);
   }
 }
 
 // One trust-region candidate at the current radius: pick the step from
 // the stored Krylov path, retract, evaluate f, run the acceptance test.
 // Every kernel is guarded by ST_TCG_STOP.
+//
+// Fused (default): two launches, k_candidate and the f evaluation whose
+// last block runs the acceptance test. With publish (end of a solve
+// sequence) that kernel also copies the control block to the host and
+// releases F_SOLVE_OUT; it then is the sequence's last node. DPO_NO_CF=1:
+// the five standalone launches, and publishing is left to the caller.
+static void launch_candidate(double* ctrl, double* step, const double* eta,
+                             const double* eta_snap,
+                             const double* delta_snap, const double* X,
+                             double* Xprop, int n, int d, int r,
+                             hipStream_t s) {
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_candidate<Dc, Rc>), dim3(blocks_for(n, 256)),
+                           dim3(256), 0, s, ctrl, step, eta, eta_snap,
+                           delta_snap, X, Xprop, n);
+      }))
+    dpo_bad_shape(d, r);
+}
+
 static void enqueue_candidate(DpoCtx* c, const double* X, double accept_rho,
-                              hipStream_t s) {
-  dpo_ctrl_candidate(c->ctrl, s);
-  dpo_form_step(c->step, c->eta, c->eta_snap, c->delta_snap, c->ctrl,
-                c->total, s);
-  launch_polar(X, c->step, nullptr, 1.0, 1.0, 0.0, c->Xprop, c->n, c->d,
-               c->r, c->ctrl, ST_TCG_STOP, s);
-  ctx_hess<1>(c, c->Xprop, nullptr, c->Gt, nullptr, nullptr, C_DOT0, C_DOT2,
-              ST_TCG_STOP, s);
-  dpo_ctrl_accept(c->ctrl, accept_rho, s);
+                              hipStream_t s, bool publish = false) {
+  if (!ctx_fuse_scalar(c)) {
+    dpo_ctrl_candidate(c->ctrl, s);
+    dpo_form_step(c->step, c->eta, c->eta_snap, c->delta_snap, c->ctrl,
+                  c->total, s);
+    launch_polar(X, c->step, nullptr, 1.0, 1.0, 0.0, c->Xprop, c->n, c->d,
+                 c->r, c->ctrl, ST_TCG_STOP, s);
+    ctx_hess<1>(c, c->Xprop, nullptr, c->Gt, nullptr, nullptr, C_DOT0,
+                C_DOT2, ST_TCG_STOP, s);
+    dpo_ctrl_accept(c->ctrl, accept_rho, s);
+    return;
+  }
+  launch_candidate(c->ctrl, c->step, c->eta, c->eta_snap, c->delta_snap, X,
+                   c->Xprop, c->n, c->d, c->r, s);
+  TailArgs ta;
+  ta.a = accept_rho;
+  if (publish) {
+    ta.dst = c->ctrl_host_dev;
+    ta.fence = c->fences + F_SOLVE_OUT;
+    ctx_hess<1, CF_ACCEPT_OUT>(c, c->Xprop, nullptr, c->Gt, nullptr, nullptr,
+                               C_DOT0, C_DOT2, ST_TCG_STOP, s, -1, nullptr,
+                               nullptr, ta);
+  } else {
+    ctx_hess<1, CF_ACCEPT>(c, c->Xprop, nullptr, c->Gt, nullptr, nullptr,
+                           C_DOT0, C_DOT2, ST_TCG_STOP, s, -1, nullptr,
+                           nullptr, ta);
+  }
 }
 
 static void ctx_ctrl_to_host(DpoCtx* c, hipStream_t s) {
@@ -2266,9 +2613,11 @@ static void ctx_ctrl_to_host(DpoCtx* c, hipStream_t s) {
 // the host reads ST_RUN.
 static void enqueue_solve_tail(DpoCtx* c, double* X, double accept_rho,
                                hipStream_t s) {
-  enqueue_candidate(c, X, accept_rho, s);
-  ctx_ctrl_to_host(c, s);
-  fence_signal(c, F_SOLVE_OUT, s);  // last node: mark sequence complete
+  enqueue_candidate(c, X, accept_rho, s, /*publish=*/true);
+  if (!ctx_fuse_scalar(c)) {
+    ctx_ctrl_to_host(c, s);
+    fence_signal(c, F_SOLVE_OUT, s);  // last node: mark sequence complete
+  }
 }
 
 // Primary sequence: head + `iters` tCG iterations + tail. The max_inner
@@ -2493,6 +2842,103 @@ int dpo_round_solve_finish(void* h, int max_shrink, double* stats_out,
                            (hipStream_t)join_stream);
 }
 
+// The device control block, copied out synchronously (tests: every slot,
+// where the host copy a solve publishes may be a prefix). Writes at
+// most `cap` slots; returns CTRL_SIZE.
+int dpo_ctx_ctrl(void* h, double* out, int cap) {
+  DpoCtx* c = (DpoCtx*)h;
+  const int m = cap < CTRL_SIZE ? cap : CTRL_SIZE;
+  DPO_CHECK(hipDeviceSynchronize());
+  DPO_CHECK(hipMemcpy(out, c->ctrl, m * sizeof(double),
+                      hipMemcpyDeviceToHost));
+  return CTRL_SIZE;
+}
+
+// --- the fused stages as stand-alone ops (tests) ---------------------
+// k_candidate on caller-owned buffers; equals dpo_ctrl_candidate +
+// dpo_form_step + dpo_polar_affine(X, step, 1, 1, guard ST_TCG_STOP).
+void dpo_candidate(double* ctrl, double* step, const double* eta,
+                   const double* eta_snap, const double* delta_snap,
+                   const double* X, double* Xprop, int n, int d, int r,
+                   void* stream) {
+  launch_candidate(ctrl, step, eta, eta_snap, delta_snap, X, Xprop, n, d, r,
+                   (hipStream_t)stream);
+}
+
+// One Hessian stage with its scalar step, fused into the kernel's last
+// block (fused != 0) or as the launch of its own that DPO_NO_CF=1 runs.
+//   kind 1  solve head: out = grad, out2 = its copy, then the control
+//           init with tol = a, Delta0 = b (theta = 1, kappa = 0.1)
+//   kind 2  candidate evaluation of V (guard ST_TCG_STOP), then the
+//           acceptance test with accept_rho = a
+//   kind 3  evaluation: out = grad, then out3[0..2] and the dot clean-up
+void dpo_hess_tail(const int* rp, const int* ci, const double* vals,
+                   const double* V, const double* G, double* out,
+                   double* out2, double* ctrl, int n, int d, int r,
+                   int kind, int fused, double a, double b, double* out3,
+                   void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int s3 = G ? C_DOT2 : -1;
+  TailArgs ta;
+  ta.a = a; ta.b = b; ta.c = 1.0; ta.d = 0.1; ta.dst = out3;
+  if (kind == 1) {
+    if (fused) {
+      launch_hess_fused<0, CF_INIT, 1>(rp, ci, vals, V, V, G, out, nullptr,
+                                       ctrl, n, d, r, C_DOT1, C_DOT0, -1, s,
+                                       s3, out2, nullptr, ta);
+    } else {
+      launch_hess_fused<0, CF_NONE, 1>(rp, ci, vals, V, V, G, out, nullptr,
+                                       ctrl, n, d, r, C_DOT1, C_DOT0, -1, s,
+                                       s3, out2, nullptr);
+      dpo_ctrl_init(ctrl, a, b, 1.0, 0.1, stream);
+    }
+  } else if (kind == 2) {
+    if (fused) {
+      launch_hess_fused<1, CF_ACCEPT>(rp, ci, vals, V, nullptr, G, nullptr,
+                                      nullptr, ctrl, n, d, r, C_DOT0, C_DOT2,
+                                      ST_TCG_STOP, s, -1, nullptr, nullptr,
+                                      ta);
+    } else {
+      launch_hess_fused<1>(rp, ci, vals, V, nullptr, G, nullptr, nullptr,
+                           ctrl, n, d, r, C_DOT0, C_DOT2, ST_TCG_STOP, s);
+      dpo_ctrl_accept(ctrl, a, stream);
+    }
+  } else if (kind == 3) {
+    if (fused) {
+      launch_hess_fused<0, CF_EVAL>(rp, ci, vals, V, V, G, out, nullptr,
+                                    ctrl, n, d, r, C_DOT1, C_DOT0, -1, s, s3,
+                                    nullptr, nullptr, ta);
+    } else {
+      launch_hess_fused<0>(rp, ci, vals, V, V, G, out, nullptr, ctrl, n, d,
+                           r, C_DOT1, C_DOT0, -1, s, s3);
+      hipLaunchKernelGGL(k_eval_combine, dim3(1), dim3(64), 0, s, ctrl,
+                         out3);
+    }
+  } else {
+    fprintf(stderr, "dpo_hess_tail: unknown kind %d\n", kind);
+    abort();
+  }
+}
+
+// The tCG Hd stage on caller-owned buffers: Hd = P_X(Q delta) with
+// delta = C_BETA * delta_old - z, <delta, Hd> and the alpha tail (status
+// ST_RUN only). fused != 0: one kernel, delta_old read from buffer
+// 1 - (C_ITER & 1) of (d0, d1) and delta written to the other.
+// fused == 0: k_tcg_delta in place on d0, then the Hessian kernel on it.
+void dpo_hd_stage(const int* rp, const int* ci, const double* vals,
+                  double* d0, double* d1, const double* z, const double* X,
+                  double* Hd, double* ctrl, int n, int d, int r, int fused,
+                  void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (fused) {
+    launch_hd_folded(rp, ci, vals, d0, d1, z, X, Hd, ctrl, n, d, r, s);
+  } else {
+    dpo_tcg_delta(d0, z, ctrl, (long)n * (d + 1) * r, stream);
+    launch_hess_fused<0, CF_ALPHA>(rp, ci, vals, d0, X, nullptr, Hd, d0,
+                                   ctrl, n, d, r, C_DOT0, -1, ST_RUN, s);
+  }
+}
+
 // tCG iterations in the primary solve graph of this context, for the
 // problem currently bound (DPO_TCG_SEG resolved); == max_inner: one graph.
 int dpo_tcg_segment(void* h) { return solve_segment((DpoCtx*)h); }
@@ -2509,6 +2955,32 @@ int dpo_ctx_counters(void* h, long* out, int cap) {
   return len;
 }
 
+}  // extern "C"
+
+// The evaluation's kernels. Fused (default): the gradient kernel's last
+// block writes the three scalars, cleans the dot slots and, with a
+// fence, releases it. DPO_NO_CF=1: k_eval_combine, and k_fence_signal
+// for the fence, as launches of their own.
+static void eval_terms(DpoCtx* c, const double* X, double* out_dev,
+                       hipStream_t s, unsigned int* fence) {
+  if (!ctx_fuse_scalar(c)) {
+    ctx_hess<0>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0, -1, s,
+                c->Gt ? C_DOT2 : -1);
+    hipLaunchKernelGGL(k_eval_combine, dim3(1), dim3(64), 0, s, c->ctrl,
+                       out_dev);
+    if (fence)
+      hipLaunchKernelGGL(k_fence_signal, dim3(1), dim3(64), 0, s, fence);
+    return;
+  }
+  TailArgs ta;
+  ta.dst = out_dev;
+  ta.fence = fence;
+  ctx_hess<0, CF_EVAL>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0, -1,
+                       s, c->Gt ? C_DOT2 : -1, nullptr, nullptr, ta);
+}
+
+extern "C" {
+
 // Per-round evaluation: out_dev (>=3 doubles, device) = [f, 0.5<X,G>, gn2]
 // using the ctx's problem pointers. No host sync.
 void dpo_eval_terms(void* h, const double* X, double* out_dev,
@@ -2521,10 +2993,7 @@ void dpo_eval_terms(void* h, const double* X, double* out_dev,
   // <P,P> / <QX+G,X> / <G,X> (the standalone <G,X> k_dots re-read
   // 2x the iterate from HBM and was the eval phase's fattest kernel
   // at 1M poses — profiles/r2c_narrow)
-  ctx_hess<0>(c, X, X, c->Gt, c->grad, nullptr, C_DOT1, C_DOT0, -1, s,
-              c->Gt ? C_DOT2 : -1);
-  hipLaunchKernelGGL(k_eval_combine, dim3(1), dim3(64), 0, s, c->ctrl,
-                     out_dev);
+  eval_terms(c, X, out_dev, s, nullptr);
 }
 
 
@@ -2553,8 +3022,8 @@ static void enqueue_eval_body(DpoCtx* c, const double* X, const double* nbr,
                               double* out_dev, hipStream_t s) {
   fence_wait(c, F_EVAL_IN, s);
   ctx_assemble_g(c, nbr, s);
-  dpo_eval_terms((void*)c, X, out_dev, (void*)s);
-  fence_signal(c, F_EVAL_OUT, s);
+  // the OUT fence is released by the evaluation's last kernel
+  eval_terms(c, X, out_dev, s, c->fences + F_EVAL_OUT);
 }
 
 // IN fence must already be signalled on the producer stream. With

@@ -83,6 +83,13 @@ _lib.dpo_group_solve_start.argtypes = [
 _lib.dpo_group_solve_finish.argtypes = [
     _c, ctypes.POINTER(ctypes.c_int), _i, _i, _c]
 _lib.dpo_group_eval.argtypes = [_c, _c, _l, _c]
+_lib.dpo_ctx_ctrl.restype = _i
+_lib.dpo_ctx_ctrl.argtypes = [_c, ctypes.POINTER(ctypes.c_double), _i]
+_lib.dpo_hd_stage.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c, _i, _i,
+                              _i, _i, _c]
+_lib.dpo_candidate.argtypes = [_c, _c, _c, _c, _c, _c, _c, _i, _i, _i, _c]
+_lib.dpo_hess_tail.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _i, _i, _i,
+                               _i, _i, _d, _d, _c, _c]
 
 CTRL_SIZE = _lib.dpo_ctrl_size()
 
@@ -360,6 +367,83 @@ def dots(A: Tensor, B: Tensor, C: Optional[Tensor], ctrl: Tensor,
                   guard, _stream(A))
 
 
+def candidate(ctrl: Tensor, step: Tensor, eta: Tensor, eta_snap: Tensor,
+              delta_snap: Tensor, X: Tensor, Xprop: Tensor, d: int) -> None:
+    """One trust-region candidate in one launch (status ST_TCG_STOP
+    only): the selection of dpo_ctrl_candidate, the step of form_step
+    and Xprop = polar(X + step)."""
+    for t in (ctrl, step, eta, eta_snap, delta_snap, X, Xprop):
+        _chk(t)
+    r = X.shape[-1]
+    _check_shape(d, r)
+    total = X.numel()
+    n = total // ((d + 1) * r)
+    assert step.numel() == eta.numel() == Xprop.numel() == total
+    assert eta_snap.numel() == delta_snap.numel()
+    assert eta_snap.numel() % total == 0 and ctrl.numel() >= CTRL_SIZE
+    _lib.dpo_candidate(_p(ctrl), _p(step), _p(eta), _p(eta_snap),
+                       _p(delta_snap), _p(X), _p(Xprop), n, d, r, _stream(X))
+
+
+def hd_stage(Q, d0: Tensor, d1: Optional[Tensor], z: Tensor, X: Tensor,
+             Hd: Tensor, ctrl: Tensor, d: int, fused: bool) -> None:
+    """The tCG Hd stage (status ST_RUN only): delta = C_BETA * delta_old
+    - z, Hd = P_X(Q delta), <delta, Hd> and the alpha step. fused: one
+    kernel that reads delta_old from buffer 1 - (C_ITER & 1) of (d0, d1)
+    and writes delta into the other; else tcg_delta in place on d0
+    followed by the Hessian kernel."""
+    for t in (d0, z, X, Hd, ctrl):
+        _chk(t)
+    r = X.shape[-1]
+    _check_shape(d, r)
+    n = X.numel() // ((d + 1) * r)
+    assert Q.n == n and ctrl.numel() >= CTRL_SIZE
+    assert d0.numel() == z.numel() == Hd.numel() == X.numel()
+    if fused:
+        _chk(d1)
+        assert d1.numel() == X.numel()
+    _lib.dpo_hd_stage(_p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals), _p(d0),
+                      _p(d1), _p(z), _p(X), _p(Hd), _p(ctrl), n, d, r,
+                      1 if fused else 0, _stream(X))
+
+
+HESS_TAIL_INIT, HESS_TAIL_ACCEPT, HESS_TAIL_EVAL = 1, 2, 3
+
+
+def hess_tail(Q, V: Tensor, G: Optional[Tensor], ctrl: Tensor, d: int,
+              kind: int, fused: bool, a: float = 0.0, b: float = 0.0,
+              out: Optional[Tensor] = None, out2: Optional[Tensor] = None,
+              out3: Optional[Tensor] = None) -> None:
+    """One Hessian stage of the solve or the evaluation together with the
+    scalar step behind it: run by the kernel's last block (fused) or as
+    the separate launch of the unfused sequence.
+      HESS_TAIL_INIT    out = grad f(V), out2 = copy; control init with
+                        tol = a, Delta0 = b
+      HESS_TAIL_ACCEPT  f(V) dots (status ST_TCG_STOP only); acceptance
+                        test with accept_rho = a
+      HESS_TAIL_EVAL    out = grad f(V); out3 = [f, 0.5 <V, G>, gn^2]"""
+    _chk(V); _chk(ctrl)
+    r = V.shape[-1]
+    _check_shape(d, r)
+    n = V.numel() // ((d + 1) * r)
+    assert Q.n == n and ctrl.numel() >= CTRL_SIZE
+    assert kind in (HESS_TAIL_INIT, HESS_TAIL_ACCEPT, HESS_TAIL_EVAL)
+    for t in (G, out, out2):
+        if t is not None:
+            _chk(t)
+            assert t.numel() == V.numel()
+    if kind != HESS_TAIL_ACCEPT:
+        assert out is not None
+    if kind == HESS_TAIL_INIT:
+        assert out2 is not None
+    if kind == HESS_TAIL_EVAL:
+        assert out3 is not None and out3.numel() >= 3
+        _chk(out3)
+    _lib.dpo_hess_tail(_p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals), _p(V),
+                       _p(G), _p(out), _p(out2), _p(ctrl), n, d, r, kind,
+                       1 if fused else 0, a, b, _p(out3), _stream(V))
+
+
 # ---------------------------------------------------------------------
 # Device-resident RBCD local solve
 # ---------------------------------------------------------------------
@@ -439,6 +523,13 @@ class DeviceSolver:
         assert n == len(buf)
         return {"solves": int(buf[0]), "continuations": int(buf[1]),
                 "hlen_hist": [int(v) for v in buf[2:]]}
+
+    def ctrl_block(self) -> list:
+        """The device control block, all CTRL_SIZE slots (synchronises)."""
+        buf = (ctypes.c_double * CTRL_SIZE)()
+        assert _lib.dpo_ctx_ctrl(self.handle, buf, CTRL_SIZE) \
+            == CTRL_SIZE
+        return list(buf)
 
     def eval_terms(self, problem, X: Tensor) -> Tensor:
         """Device 3-vector [f(X), 0.5<X,G>, ||rgrad||^2]; no host sync."""
