@@ -241,3 +241,203 @@ def cert_contract(V: Tensor, C: Tensor) -> None:
     carry = V[b].clone()
     V[:k] = new
     V[k] = carry
+
+
+# ---------------------------------------------------------------------
+# refine: global Riemannian trust region on f(X) = 0.5 <Q, X^T X>
+# (docs/DESIGN.md §17). The control array mirrors RefSlot in dpo_ops.hip;
+# the functions below are the fp64 reference of the HIP stages, with the
+# scalar steps in the order of k_ref_ctl.
+# ---------------------------------------------------------------------
+(RF_STATUS, RF_FX, RF_GN2, RF_RR, RF_ZR, RF_EPE, RF_EPD, RF_DPD, RF_COEF,
+ RF_BETA, RF_ITER, RF_RADIUS, RF_BOUND, RF_DM, RF_STOP, RF_TCG, RF_FPROP,
+ RF_RHO, RF_ACCEPTED, RF_GRAD_TOL, RF_MAX_INNER, RF_MAX_RADIUS, RF_OUTER,
+ RF_INNER, RF_REJECTED, RF_STREAK, RF_HIT, RF_DHD) = range(28)
+RF_SIZE = 32
+RS_RUN, RS_TCG_DONE, RS_CONVERGED, RS_HEAD = range(4)
+RT_NONE, RT_CONVERGED, RT_EXCEEDED_TR, RT_NEG_CURV, RT_MAX_INNER = range(5)
+REFINE_TCG_NAMES = ("none", "converged", "exceeded_tr", "negative_curvature",
+                    "max_inner")
+# workspace vectors, in the order the HIP entry point takes them
+REFINE_BUFS = ("X", "Xp", "QV", "grad", "eta", "r", "z", "delta", "Hd")
+
+
+class RefineWorkspace:
+    """Caller-owned buffers of one refinement: the nine (N, r) vectors of
+    REFINE_BUFS (X is the iterate, a copy of the Xt given) and the
+    per-block partial slots of the HIP kernels."""
+
+    def __init__(self, Xt: Tensor):
+        assert Xt.dim() == 2 and Xt.dtype == torch.float64
+        self.X = Xt.detach().clone().contiguous()
+        for name in REFINE_BUFS[1:]:
+            setattr(self, name, torch.zeros_like(self.X))
+        self.part = torch.zeros(2 * CERT_BLOCK, dtype=torch.float64,
+                                device=Xt.device)
+
+    def bufs(self):
+        return [getattr(self, name) for name in REFINE_BUFS]
+
+
+def refine_control(grad_tol: float, Delta0: float, max_inner: int,
+                   device="cpu") -> Tensor:
+    """A fresh control array: status RS_HEAD, radius Delta0 (capped at
+    5 Delta0 when it grows), everything else zero."""
+    if max_inner < 1:
+        raise ValueError("max_inner must be at least 1")
+    h = torch.zeros(RF_SIZE, dtype=torch.float64)
+    h[RF_STATUS] = RS_HEAD
+    h[RF_GRAD_TOL] = grad_tol
+    h[RF_RADIUS] = Delta0
+    h[RF_MAX_RADIUS] = 5.0 * Delta0
+    h[RF_MAX_INNER] = max_inner
+    return h.to(device)
+
+
+def _refine_precond(pre, X: Tensor, V: Tensor, d: int) -> Tensor:
+    """z = P_X(M^-1 V); pre = (mode, data): ("jacobi", L (n, dh, dh)),
+    ("dense", Minv (N, N) fp32) or, CPU only, ("exact", scipy splu)."""
+    mode, data = pre
+    if mode == "jacobi":
+        return precond_apply(data, X, V, d)
+    if mode == "dense":
+        # fp32 storage, fp64 accumulation, as k_precond_dense
+        Z = data.to(torch.float64) @ V
+    elif mode == "exact":
+        Z = torch.from_numpy(data.solve(V.numpy()))
+    else:
+        raise ValueError(f"unknown preconditioner mode {mode!r}")
+    return tangent_project(X, Z, d)
+
+
+def _dot(a: Tensor, b: Tensor) -> float:
+    return float((a * b).sum())
+
+
+def refine_hd_stage(Q, ws: RefineWorkspace, ctl: Tensor, d: int) -> None:
+    """Hd = P_X(Q delta) and part[0] = <delta, Hd> (status RS_RUN only;
+    the HIP version leaves per-block partials in ws.part instead)."""
+    if float(ctl[RF_STATUS]) != RS_RUN:
+        return
+    ws.QV.copy_(torch.sparse.mm(Q.to_scalar_csr(), ws.delta))
+    ws.Hd.copy_(tangent_project(ws.X, ws.QV, d))
+    ws.part[0] = _dot(ws.delta, ws.Hd)
+
+
+def refine_head(Q, ws: RefineWorkspace, ctl: Tensor, d: int, pre) -> None:
+    """Head of an outer step (status RS_HEAD only): grad = P_X(Q X), f,
+    ||grad||^2, the tCG bound; status RS_CONVERGED when ||grad|| <=
+    grad_tol, else RS_RUN with r = grad, eta = 0, z0 and delta0 = -z0."""
+    if float(ctl[RF_STATUS]) != RS_HEAD:
+        return
+    ws.QV.copy_(torch.sparse.mm(Q.to_scalar_csr(), ws.X))
+    s0 = _dot(ws.QV, ws.X)
+    ws.grad.copy_(tangent_project(ws.X, ws.QV, d))
+    ws.r.copy_(ws.grad)
+    ws.eta.zero_()
+    s1 = _dot(ws.grad, ws.grad)
+    nr0 = s1 ** 0.5
+    ctl[RF_FX] = 0.5 * s0
+    ctl[RF_GN2] = s1
+    ctl[RF_RR] = s1
+    ctl[RF_BOUND] = nr0 * min(nr0, 0.1)
+    # RF_TCG keeps how the last tCG ended until the next one ends
+    for slot in (RF_EPE, RF_EPD, RF_COEF, RF_BETA, RF_ITER, RF_DM, RF_STOP,
+                 RF_HIT):
+        ctl[slot] = 0.0
+    if nr0 <= float(ctl[RF_GRAD_TOL]):
+        ctl[RF_STATUS] = RS_CONVERGED
+        return
+    ctl[RF_STATUS] = RS_RUN
+    ws.z.copy_(_refine_precond(pre, ws.X, ws.r, d))
+    zr = _dot(ws.z, ws.r)
+    ctl[RF_ZR] = zr
+    ctl[RF_DPD] = zr
+    ws.delta.copy_(-ws.z)
+
+
+def refine_tcg_steps(Q, ws: RefineWorkspace, ctl: Tensor, d: int, pre,
+                     nsteps: int) -> None:
+    """nsteps tCG iterations, each a no-op unless the status is RS_RUN.
+    An iteration that meets the boundary or negative curvature, converges
+    or reaches max_inner sets RS_TCG_DONE and RF_TCG."""
+    for _ in range(nsteps):
+        if float(ctl[RF_STATUS]) != RS_RUN:
+            return
+        refine_hd_stage(Q, ws, ctl, d)
+        c = ctl.tolist()
+        d_Hd, z_r = float(ws.part[0]), c[RF_ZR]
+        e_Pe, e_Pd, d_Pd = c[RF_EPE], c[RF_EPD], c[RF_DPD]
+        rad2 = c[RF_RADIUS] * c[RF_RADIUS]
+        if d_Hd != 0.0:
+            alpha = z_r / d_Hd
+        else:   # IEEE division, as on the device
+            alpha = float("nan") if z_r == 0.0 or z_r != z_r else \
+                float("inf") * (1.0 if z_r > 0 else -1.0)
+        e_Pe_new = e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd
+        ctl[RF_DHD] = d_Hd
+        ctl[RF_ITER] = c[RF_ITER] + 1.0
+        ctl[RF_INNER] = c[RF_INNER] + 1.0
+        if d_Hd <= 0.0 or e_Pe_new >= rad2:
+            disc = e_Pd * e_Pd + d_Pd * (rad2 - e_Pe)
+            tau = (-e_Pd + max(disc, 0.0) ** 0.5) / d_Pd if d_Pd > 0.0 \
+                else 0.0
+            ctl[RF_COEF] = tau
+            ctl[RF_DM] = c[RF_DM] + (tau * z_r - 0.5 * tau * tau * d_Hd)
+            ctl[RF_STOP] = 1.0
+            ctl[RF_TCG] = RT_NEG_CURV if d_Hd <= 0.0 else RT_EXCEEDED_TR
+            ws.eta.add_(ws.delta, alpha=tau)
+            ctl[RF_HIT] = 1.0
+            ctl[RF_STATUS] = RS_TCG_DONE
+            return
+        ctl[RF_COEF] = alpha
+        ctl[RF_EPE] = e_Pe_new
+        ctl[RF_DM] = c[RF_DM] + 0.5 * alpha * z_r
+        ws.eta.add_(ws.delta, alpha=alpha)
+        ws.r.add_(ws.Hd, alpha=alpha)
+        rr = _dot(ws.r, ws.r)
+        ctl[RF_RR] = rr
+        if rr ** 0.5 <= c[RF_BOUND]:
+            ctl[RF_TCG] = RT_CONVERGED
+            ctl[RF_STATUS] = RS_TCG_DONE
+            return
+        if c[RF_ITER] + 1.0 >= c[RF_MAX_INNER]:
+            ctl[RF_TCG] = RT_MAX_INNER
+            ctl[RF_STATUS] = RS_TCG_DONE
+            return
+        ws.z.copy_(_refine_precond(pre, ws.X, ws.r, d))
+        zr_new = _dot(ws.z, ws.r)
+        beta = zr_new / z_r
+        ctl[RF_BETA] = beta
+        ctl[RF_EPD] = beta * (e_Pd + alpha * d_Pd)
+        ctl[RF_DPD] = zr_new + beta * beta * d_Pd
+        ctl[RF_ZR] = zr_new
+        ws.delta.mul_(beta).sub_(ws.z)
+
+
+def refine_candidate(Q, ws: RefineWorkspace, ctl: Tensor, d: int) -> None:
+    """Candidate stage (status RS_TCG_DONE only): Xp = retract(X, eta),
+    f(Xp), rho, the radius update and the acceptance test; an accepted Xp
+    is copied into X. Leaves status RS_HEAD."""
+    if float(ctl[RF_STATUS]) != RS_TCG_DONE:
+        return
+    ws.Xp.copy_(retract(ws.X, ws.eta, d))
+    ws.QV.copy_(torch.sparse.mm(Q.to_scalar_csr(), ws.Xp))
+    c = ctl.tolist()
+    fprop, fX = 0.5 * _dot(ws.QV, ws.Xp), c[RF_FX]
+    rho = (fX - fprop) / max(c[RF_DM], 1e-300)
+    ctl[RF_FPROP] = fprop
+    ctl[RF_RHO] = rho
+    if rho < 0.25:
+        ctl[RF_RADIUS] = c[RF_RADIUS] * 0.25
+    elif rho > 0.75 and c[RF_HIT] != 0.0:
+        ctl[RF_RADIUS] = min(2.0 * c[RF_RADIUS], c[RF_MAX_RADIUS])
+    acc = rho > 0.1 and fprop <= fX
+    ctl[RF_ACCEPTED] = 1.0 if acc else 0.0
+    ctl[RF_STREAK] = 0.0 if acc else c[RF_STREAK] + 1.0
+    if not acc:
+        ctl[RF_REJECTED] = c[RF_REJECTED] + 1.0
+    ctl[RF_OUTER] = c[RF_OUTER] + 1.0
+    ctl[RF_STATUS] = RS_HEAD
+    if acc:
+        ws.X.copy_(ws.Xp)

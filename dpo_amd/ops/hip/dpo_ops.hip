@@ -3722,3 +3722,424 @@ int dpo_cert_max_part() { return CERT_MAX_PART; }
 int dpo_cert_keep_max() { return CERT_KEEP_MAX; }
 
 }  // extern "C"
+
+// =====================================================================
+// refine: device-resident global Riemannian trust region on
+// f(X) = 0.5 <Q, X^T X> (docs/DESIGN.md §17). Steihaug-Toint
+// preconditioned tCG with the scalar logic of solver.truncated_cg /
+// trust_region batch mode, no Krylov history and no cap on the inner
+// iterations: the model decrease is a scalar recurrence.
+//
+// Execution model of the certificate: eager launches, a control array
+// `rc` of its own, every kernel guarded by rc[RF_STATUS], per-block
+// partials in fixed slots summed by cert_sum_partials in the one-block
+// control kernel that follows (a later launch, so the kernel boundary
+// publishes them). No floating-point atomics in any refine kernel.
+// Q @ V is k_bsr_spmm itself (guarded by the same slot 0).
+// =====================================================================
+enum RefSlot {
+  RF_STATUS = 0,   // RefStatus; slot 0 so that the guards of k_bsr_spmm,
+                   // k_polar_affine and k_precond_dense read it
+  RF_FX = 1, RF_GN2 = 2, RF_RR = 3, RF_ZR = 4, RF_EPE = 5, RF_EPD = 6,
+  RF_DPD = 7, RF_COEF = 8, RF_BETA = 9,
+  RF_ITER = 10,      // Hd applications of the current tCG
+  RF_RADIUS = 11, RF_BOUND = 12,
+  RF_DM = 13,        // model decrease of eta (scalar recurrence)
+  RF_STOP = 14,      // boundary / negative curvature met in this iteration
+  RF_TCG = 15,       // RefTcg: how the last tCG ended
+  RF_FPROP = 16, RF_RHO = 17, RF_ACCEPTED = 18,
+  RF_GRAD_TOL = 19, RF_MAX_INNER = 20, RF_MAX_RADIUS = 21,
+  RF_OUTER = 22,     // candidates evaluated
+  RF_INNER = 23,     // Hd applications over all outer steps
+  RF_REJECTED = 24, RF_STREAK = 25,  // rejections: total, in a row
+  RF_HIT = 26,       // last tCG ended on the boundary
+  RF_DHD = 27,       // last <delta, Hd>
+  RF_SIZE = 32,
+};
+enum RefStatus { RS_RUN = 0, RS_TCG_DONE = 1, RS_CONVERGED = 2,
+                 RS_HEAD = 3 };
+enum RefTcg { RT_NONE = 0, RT_CONVERGED = 1, RT_EXCEEDED_TR = 2,
+              RT_NEG_CURV = 3, RT_MAX_INNER = 4 };
+enum RefStage { RG_HEAD = 0, RG_Z0 = 1, RG_ALPHA = 2, RG_RR = 3,
+                RG_BETA = 4, RG_ACCEPT = 5 };
+
+__device__ __forceinline__ bool ref_off(const double* rc, int status) {
+  return rc[RF_STATUS] != (double)status;
+}
+
+// The scalar step between two vector kernels: one block sums the
+// partials of the launch before it (s0 from part[0..np), s1 from
+// part[CERT_MAX_PART..+np)) and thread 0 advances the control array.
+__global__ void k_ref_ctl(double* __restrict__ rc,
+                          const double* __restrict__ part, int np,
+                          int stage) {
+  const int want = stage == RG_HEAD ? RS_HEAD
+                   : stage == RG_ACCEPT ? RS_TCG_DONE : RS_RUN;
+  if (ref_off(rc, want)) return;
+  const double s0 = cert_sum_partials(part, np);
+  const double s1 =
+      stage == RG_HEAD ? cert_sum_partials(part + CERT_MAX_PART, np) : 0.0;
+  if (threadIdx.x != 0) return;
+  switch (stage) {
+    case RG_HEAD: {
+      // s0 = <QX, X>, s1 = ||grad||^2; theta = 1, kappa = 0.1
+      const double nr0 = sqrt(s1);
+      rc[RF_FX] = 0.5 * s0;
+      rc[RF_GN2] = s1;
+      rc[RF_RR] = s1;
+      rc[RF_BOUND] = nr0 * fmin(nr0, 0.1);
+      rc[RF_EPE] = 0.0;
+      rc[RF_EPD] = 0.0;
+      rc[RF_COEF] = 0.0;
+      rc[RF_BETA] = 0.0;
+      rc[RF_ITER] = 0.0;
+      rc[RF_DM] = 0.0;
+      rc[RF_STOP] = 0.0;
+      rc[RF_HIT] = 0.0;  // RF_TCG keeps the last tCG's ending
+      rc[RF_STATUS] =
+          nr0 <= rc[RF_GRAD_TOL] ? (double)RS_CONVERGED : (double)RS_RUN;
+      break;
+    }
+    case RG_Z0:  // s0 = <z0, r0>
+      rc[RF_ZR] = s0;
+      rc[RF_DPD] = s0;
+      break;
+    case RG_ALPHA: {  // s0 = <delta, Hd>
+      const double d_Hd = s0, z_r = rc[RF_ZR];
+      const double e_Pe = rc[RF_EPE], e_Pd = rc[RF_EPD], d_Pd = rc[RF_DPD];
+      const double rad2 = rc[RF_RADIUS] * rc[RF_RADIUS];
+      const double alpha = z_r / d_Hd;
+      const double e_Pe_new =
+          e_Pe + 2.0 * alpha * e_Pd + alpha * alpha * d_Pd;
+      rc[RF_DHD] = d_Hd;
+      rc[RF_ITER] += 1.0;
+      rc[RF_INNER] += 1.0;
+      if (d_Hd <= 0.0 || e_Pe_new >= rad2) {
+        const double disc = e_Pd * e_Pd + d_Pd * (rad2 - e_Pe);
+        const double tau =
+            d_Pd > 0.0 ? (-e_Pd + sqrt(fmax(disc, 0.0))) / d_Pd : 0.0;
+        rc[RF_COEF] = tau;
+        rc[RF_DM] += tau * z_r - 0.5 * tau * tau * d_Hd;
+        rc[RF_STOP] = 1.0;
+        rc[RF_TCG] =
+            d_Hd <= 0.0 ? (double)RT_NEG_CURV : (double)RT_EXCEEDED_TR;
+      } else {
+        rc[RF_COEF] = alpha;
+        rc[RF_EPE] = e_Pe_new;
+        rc[RF_DM] += 0.5 * alpha * z_r;
+      }
+      break;
+    }
+    case RG_RR: {  // s0 = ||r||^2 unless a stop is pending
+      if (rc[RF_STOP] != 0.0) {
+        rc[RF_HIT] = 1.0;
+        rc[RF_STATUS] = (double)RS_TCG_DONE;
+        break;
+      }
+      rc[RF_RR] = s0;
+      if (sqrt(s0) <= rc[RF_BOUND]) {
+        rc[RF_TCG] = (double)RT_CONVERGED;
+        rc[RF_STATUS] = (double)RS_TCG_DONE;
+      } else if (rc[RF_ITER] >= rc[RF_MAX_INNER]) {
+        rc[RF_TCG] = (double)RT_MAX_INNER;
+        rc[RF_STATUS] = (double)RS_TCG_DONE;
+      }
+      break;
+    }
+    case RG_BETA: {  // s0 = <z, r>
+      const double z_r = rc[RF_ZR], alpha = rc[RF_COEF];
+      const double beta = s0 / z_r;
+      rc[RF_BETA] = beta;
+      rc[RF_EPD] = beta * (rc[RF_EPD] + alpha * rc[RF_DPD]);
+      rc[RF_DPD] = s0 + beta * beta * rc[RF_DPD];
+      rc[RF_ZR] = s0;
+      break;
+    }
+    case RG_ACCEPT: {  // s0 = <Q Xp, Xp>
+      const double fprop = 0.5 * s0, fX = rc[RF_FX];
+      const double rho = (fX - fprop) / fmax(rc[RF_DM], 1e-300);
+      rc[RF_FPROP] = fprop;
+      rc[RF_RHO] = rho;
+      if (rho < 0.25)
+        rc[RF_RADIUS] *= 0.25;
+      else if (rho > 0.75 && rc[RF_HIT] != 0.0)
+        rc[RF_RADIUS] = fmin(2.0 * rc[RF_RADIUS], rc[RF_MAX_RADIUS]);
+      const bool acc = rho > 0.1 && fprop <= fX;
+      rc[RF_ACCEPTED] = acc ? 1.0 : 0.0;
+      rc[RF_STREAK] = acc ? 0.0 : rc[RF_STREAK] + 1.0;
+      if (!acc) rc[RF_REJECTED] += 1.0;
+      rc[RF_OUTER] += 1.0;
+      rc[RF_STATUS] = (double)RS_HEAD;
+      break;
+    }
+  }
+}
+
+// Per-pose stage behind Q @ V (one thread per pose, grid capped and
+// strided like the certificate's): T is the pose's tile of `in`.
+//   RP_GRAD  in = Q X: part0 += <T, X>; T = P_X(T); grad = r = T,
+//            eta = 0, part1 += ||T||^2
+//   RP_HD    in = Q delta: Hd = P_X(T); part0 += <delta, Hd>
+//   RP_Z     in = M^-1 r from the dense apply: z = P_X(T) in place;
+//            part0 += <z, r>
+//   RP_ZJ    T = block-Jacobi solve of r with the factors L; then RP_Z
+// zero, when given, has this pose's tile cleared (the j-split dense
+// apply that follows accumulates into it).
+enum RefProj { RP_GRAD = 0, RP_HD = 1, RP_Z = 2, RP_ZJ = 3 };
+
+// Launched with CERT_BS threads only: the bound lets the wide shapes keep
+// their tile in registers instead of spilling at the default 128 VGPRs.
+template <int D, int R, int MODE>
+__global__ void __launch_bounds__(CERT_BS) k_ref_proj(const double* __restrict__ rc, int status,
+                           const double* __restrict__ X,
+                           const double* in,
+                           const double* __restrict__ L,
+                           const double* __restrict__ dotw,
+                           double* out, double* __restrict__ out2,
+                           double* __restrict__ eta,
+                           double* __restrict__ zero,
+                           double* __restrict__ part, int n) {
+  if (ref_off(rc, status)) return;
+  constexpr int dh = D + 1;
+  double p0 = 0.0, p1 = 0.0;
+  for (int i = blockIdx.x * CERT_BS + threadIdx.x; i < n;
+       i += gridDim.x * CERT_BS) {
+    const size_t o = (size_t)i * dh * R;
+    const double* Xi = X + o;
+    double T[dh][R];
+    if (MODE == RP_ZJ) {
+      #pragma unroll
+      for (int k = 0; k < R; ++k) {
+        double y[dh];
+        chol_solve_col<dh>(L + (size_t)i * dh * dh, in + o + k, R, y);
+        #pragma unroll
+        for (int c = 0; c < dh; ++c) T[c][k] = y[c];
+      }
+    } else {
+      #pragma unroll
+      for (int c = 0; c < dh; ++c)
+        #pragma unroll
+        for (int k = 0; k < R; ++k) T[c][k] = in[o + c * R + k];
+    }
+    if (MODE == RP_GRAD) {
+      #pragma unroll
+      for (int c = 0; c < dh; ++c)
+        #pragma unroll
+        for (int k = 0; k < R; ++k) p0 = fma(T[c][k], Xi[c * R + k], p0);
+    }
+    tangent_project<D, R>(Xi, T);
+    #pragma unroll
+    for (int c = 0; c < dh; ++c)
+      #pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const size_t e = o + c * R + k;
+        const double t = T[c][k];
+        out[e] = t;
+        if (MODE == RP_GRAD) {
+          out2[e] = t;
+          eta[e] = 0.0;
+          p1 = fma(t, t, p1);
+        } else {
+          p0 = fma(t, dotw[e], p0);
+        }
+        if (zero != nullptr) zero[e] = 0.0;
+      }
+  }
+  const double s0 = cert_block_sum(p0);
+  if (threadIdx.x == 0) part[blockIdx.x] = s0;
+  if (MODE == RP_GRAD) {
+    const double s1 = cert_block_sum(p1);
+    if (threadIdx.x == 0) part[CERT_MAX_PART + blockIdx.x] = s1;
+  }
+}
+
+// eta += coef * delta; unless a stop is pending r += coef * Hd with the
+// block partial of ||r||^2 (and z cleared for the dense apply).
+__global__ void k_ref_update(const double* __restrict__ rc,
+                             double* __restrict__ eta,
+                             double* __restrict__ rvec,
+                             const double* __restrict__ delta,
+                             const double* __restrict__ Hd,
+                             double* __restrict__ zero,
+                             double* __restrict__ part, long total) {
+  if (ref_off(rc, RS_RUN)) return;
+  const double coef = rc[RF_COEF];
+  const bool stop = rc[RF_STOP] != 0.0;
+  double nrm = 0.0;
+  for (long e = (long)blockIdx.x * CERT_BS + threadIdx.x; e < total;
+       e += (long)gridDim.x * CERT_BS) {
+    eta[e] = fma(coef, delta[e], eta[e]);
+    if (!stop) {
+      const double rv = fma(coef, Hd[e], rvec[e]);
+      rvec[e] = rv;
+      nrm = fma(rv, rv, nrm);
+      if (zero != nullptr) zero[e] = 0.0;
+    }
+  }
+  const double s = cert_block_sum(nrm);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// delta = beta * delta - z; beta == 0 (the first direction of a tCG)
+// does not read the old delta.
+__global__ void k_ref_delta(const double* __restrict__ rc,
+                            double* __restrict__ delta,
+                            const double* __restrict__ z, long total) {
+  if (ref_off(rc, RS_RUN)) return;
+  const double beta = rc[RF_BETA];
+  for (long e = (long)blockIdx.x * CERT_BS + threadIdx.x; e < total;
+       e += (long)gridDim.x * CERT_BS)
+    delta[e] = beta == 0.0 ? -z[e] : fma(beta, delta[e], -z[e]);
+}
+
+// part[b] = block partial of <A, B> (f of the proposal)
+__global__ void k_ref_dot(const double* __restrict__ rc, int status,
+                          const double* __restrict__ A,
+                          const double* __restrict__ B,
+                          double* __restrict__ part, long total) {
+  if (ref_off(rc, status)) return;
+  double dot = 0.0;
+  for (long e = (long)blockIdx.x * CERT_BS + threadIdx.x; e < total;
+       e += (long)gridDim.x * CERT_BS)
+    dot = fma(A[e], B[e], dot);
+  const double s = cert_block_sum(dot);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// X = Xp behind an accepted candidate. Enqueued again it copies the same
+// values: Xp changes only in the next candidate stage.
+__global__ void k_ref_copy(const double* __restrict__ rc,
+                           double* __restrict__ X,
+                           const double* __restrict__ Xp, long total) {
+  if (ref_off(rc, RS_HEAD) || rc[RF_ACCEPTED] == 0.0) return;
+  for (long e = (long)blockIdx.x * CERT_BS + threadIdx.x; e < total;
+       e += (long)gridDim.x * CERT_BS)
+    X[e] = Xp[e];
+}
+
+// The refine buffers, all (N, r) but part (2 * CERT_MAX_PART) and rc.
+struct RefBufs {
+  const int *rp, *ci;
+  const double* vals;
+  double *X, *Xp, *QV, *grad, *eta, *rvec, *z, *delta, *Hd;
+  const double* L;     // block-Jacobi factors, or
+  const float* Minv;   // the dense fp32 inverse
+  double *part, *rc;
+  int n, d, r;
+};
+
+static inline void ref_ctl(const RefBufs& b, int np, int stage,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(k_ref_ctl, dim3(1), dim3(CERT_BS), 0, s, b.rc,
+                     (const double*)b.part, np, stage);
+}
+
+template <int MODE>
+static void ref_proj(const RefBufs& b, int status, const double* in,
+                     const double* dotw, double* out, double* out2,
+                     double* eta, double* zero, hipStream_t s) {
+  if (!dispatch_dr(b.d, b.r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_ref_proj<Dc, Rc, MODE>),
+                           dim3(cert_grid(b.n)), dim3(CERT_BS), 0, s,
+                           (const double*)b.rc, status,
+                           (const double*)b.X, in, b.L, dotw, out, out2,
+                           eta, zero, b.part, b.n);
+      }))
+    dpo_bad_shape(b.d, b.r);
+}
+
+// z = P_X(M^-1 r) and the partials of <z, r> (status RS_RUN)
+static void ref_precond(const RefBufs& b, hipStream_t s) {
+  if (b.Minv != nullptr) {
+    // z was cleared by the kernel that wrote r
+    launch_precond_dense(b.Minv, b.rvec, b.z, b.n * (b.d + 1), b.r, b.rc,
+                         RS_RUN, s, /*prezeroed=*/true);
+    ref_proj<RP_Z>(b, RS_RUN, b.z, b.rvec, b.z, nullptr, nullptr, nullptr,
+                   s);
+  } else {
+    ref_proj<RP_ZJ>(b, RS_RUN, b.rvec, b.rvec, b.z, nullptr, nullptr,
+                    nullptr, s);
+  }
+}
+
+static void ref_hd(const RefBufs& b, hipStream_t s) {
+  launch_spmm(b.rp, b.ci, b.vals, b.n, b.d, b.r, b.delta, b.QV, b.rc,
+              RS_RUN, s);
+  ref_proj<RP_HD>(b, RS_RUN, b.QV, b.delta, b.Hd, nullptr, nullptr,
+                  nullptr, s);
+}
+
+static void ref_enqueue_head(const RefBufs& b, hipStream_t s) {
+  const long total = (long)b.n * (b.d + 1) * b.r;
+  const int gp = cert_grid(b.n);
+  launch_spmm(b.rp, b.ci, b.vals, b.n, b.d, b.r, b.X, b.QV, b.rc, RS_HEAD,
+              s);
+  ref_proj<RP_GRAD>(b, RS_HEAD, b.QV, nullptr, b.grad, b.rvec, b.eta,
+                    b.Minv != nullptr ? b.z : nullptr, s);
+  ref_ctl(b, gp, RG_HEAD, s);
+  ref_precond(b, s);
+  ref_ctl(b, gp, RG_Z0, s);
+  hipLaunchKernelGGL(k_ref_delta, dim3(cert_grid(total)), dim3(CERT_BS), 0,
+                     s, (const double*)b.rc, b.delta, (const double*)b.z,
+                     total);
+}
+
+static void ref_enqueue_tcg(const RefBufs& b, int nsteps, hipStream_t s) {
+  const long total = (long)b.n * (b.d + 1) * b.r;
+  const int gp = cert_grid(b.n), ge = cert_grid(total);
+  for (int it = 0; it < nsteps; ++it) {
+    ref_hd(b, s);
+    ref_ctl(b, gp, RG_ALPHA, s);
+    hipLaunchKernelGGL(k_ref_update, dim3(ge), dim3(CERT_BS), 0, s,
+                       (const double*)b.rc, b.eta, b.rvec,
+                       (const double*)b.delta, (const double*)b.Hd,
+                       b.Minv != nullptr ? b.z : nullptr, b.part, total);
+    ref_ctl(b, ge, RG_RR, s);
+    ref_precond(b, s);
+    ref_ctl(b, gp, RG_BETA, s);
+    hipLaunchKernelGGL(k_ref_delta, dim3(ge), dim3(CERT_BS), 0, s,
+                       (const double*)b.rc, b.delta, (const double*)b.z,
+                       total);
+  }
+}
+
+static void ref_enqueue_candidate(const RefBufs& b, hipStream_t s) {
+  const long total = (long)b.n * (b.d + 1) * b.r;
+  const int ge = cert_grid(total);
+  launch_polar(b.X, b.eta, nullptr, 1.0, 1.0, 0.0, b.Xp, b.n, b.d, b.r,
+               b.rc, RS_TCG_DONE, s);
+  launch_spmm(b.rp, b.ci, b.vals, b.n, b.d, b.r, b.Xp, b.QV, b.rc,
+              RS_TCG_DONE, s);
+  hipLaunchKernelGGL(k_ref_dot, dim3(ge), dim3(CERT_BS), 0, s,
+                     (const double*)b.rc, (int)RS_TCG_DONE,
+                     (const double*)b.QV, (const double*)b.Xp, b.part,
+                     total);
+  ref_ctl(b, ge, RG_ACCEPT, s);
+  hipLaunchKernelGGL(k_ref_copy, dim3(ge), dim3(CERT_BS), 0, s,
+                     (const double*)b.rc, b.X, (const double*)b.Xp, total);
+}
+
+extern "C" {
+
+// stage: 0 head, 1 nsteps tCG iterations, 2 candidate, 3 the Hd stage
+// alone (Q delta, projection, partials; no control step). bufs: the nine
+// (N, r) vectors X, Xp, QV, grad, eta, r, z, delta, Hd. Exactly one of L
+// and Minv is given. Nothing synchronises.
+void dpo_refine_stage(int stage, const int* row_ptr, const int* col_idx,
+                      const double* vals, double* const* bufs,
+                      const double* L, const float* Minv, double* part,
+                      double* rc, int n, int d, int r, int nsteps,
+                      void* stream) {
+  RefBufs b{row_ptr, col_idx, vals,    bufs[0], bufs[1], bufs[2], bufs[3],
+            bufs[4], bufs[5], bufs[6], bufs[7], bufs[8], L,       Minv,
+            part,    rc,      n,       d,       r};
+  hipStream_t s = (hipStream_t)stream;
+  if (stage == 0) ref_enqueue_head(b, s);
+  else if (stage == 1) ref_enqueue_tcg(b, nsteps, s);
+  else if (stage == 2) ref_enqueue_candidate(b, s);
+  else ref_hd(b, s);
+}
+
+int dpo_refine_ctrl_size() { return RF_SIZE; }
+
+}  // extern "C"

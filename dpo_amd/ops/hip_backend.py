@@ -829,3 +829,76 @@ def cert_contract(V: Tensor, C: Tensor) -> None:
     Cp[:, :k] = C.detach().to("cpu", torch.float64)
     Cd = Cp.to(V.device)
     _lib.dpo_cert_contract(_p(V), _p(Cd), b, k, V.shape[1], _stream(V))
+
+
+# ---------------------------------------------------------------------
+# refine: device-resident global trust region (docs/DESIGN.md §17) —
+# interface mirrors cpu_ref.refine_*
+# ---------------------------------------------------------------------
+_lib.dpo_refine_stage.argtypes = [_i, _c, _c, _c,
+                                  ctypes.POINTER(ctypes.c_void_p), _c, _c,
+                                  _c, _c, _i, _i, _i, _i, _c]
+_lib.dpo_refine_ctrl_size.restype = _i
+
+from .cpu_ref import (CERT_BLOCK, RF_SIZE, RefineWorkspace,  # noqa: E402,F401
+                      refine_control)
+
+assert _lib.dpo_refine_ctrl_size() == RF_SIZE
+assert _CERT_PART == CERT_BLOCK
+
+
+def _refine_stage(stage: int, Q, ws, ctl: Tensor, d: int, pre,
+                  nsteps: int = 0) -> None:
+    bufs = ws.bufs()
+    X = bufs[0]
+    N, r = X.shape
+    n = N // (d + 1)
+    cert_check_shape(d, r)
+    _chk_q(Q, X); _chk(ctl); _chk(ws.part)
+    assert Q.n == n and Q.dh == d + 1 and N == n * (d + 1)
+    assert ctl.numel() == RF_SIZE and ws.part.numel() >= 2 * _CERT_PART
+    for t in bufs:
+        _chk(t)
+        assert t.shape == X.shape and t.device == X.device
+    L = Minv = None
+    if pre is not None:
+        mode, data = pre
+        if mode == "jacobi":
+            L = data
+            _chk(L)
+            assert L.shape == (n, d + 1, d + 1)
+        elif mode == "dense":
+            Minv = data
+            _chk(Minv, torch.float32)
+            assert Minv.shape == (N, N)
+        else:
+            raise ValueError(
+                f"preconditioner mode {mode!r} has no HIP kernel: use "
+                "'jacobi' or 'dense'")
+    ptrs = (ctypes.c_void_p * len(bufs))(*[t.data_ptr() for t in bufs])
+    _lib.dpo_refine_stage(stage, _p(Q.row_ptr), _p(Q.col_idx), _p(Q.vals),
+                          ptrs, _p(L), _p(Minv), _p(ws.part), _p(ctl), n, d,
+                          r, nsteps, _stream(X))
+
+
+def refine_head(Q, ws, ctl: Tensor, d: int, pre) -> None:
+    """cpu_ref.refine_head on the device; no host synchronisation."""
+    assert pre is not None
+    _refine_stage(0, Q, ws, ctl, d, pre)
+
+
+def refine_tcg_steps(Q, ws, ctl: Tensor, d: int, pre, nsteps: int) -> None:
+    """Enqueue nsteps tCG iterations; those past the stopping point are
+    runs of guarded no-ops."""
+    assert pre is not None and nsteps >= 0
+    _refine_stage(1, Q, ws, ctl, d, pre, nsteps)
+
+
+def refine_candidate(Q, ws, ctl: Tensor, d: int) -> None:
+    _refine_stage(2, Q, ws, ctl, d, None)
+
+
+def refine_hd_stage(Q, ws, ctl: Tensor, d: int) -> None:
+    """Hd = P_X(Q delta) with the per-block partials of <delta, Hd> in
+    ws.part[:cert_partials(n)] (status RS_RUN only)."""
+    _refine_stage(3, Q, ws, ctl, d, None)

@@ -43,6 +43,10 @@ def main():
                          "of B vectors (basis memory N (B + 1) doubles)")
     ap.add_argument("--cert-max-iters", type=int, default=None, metavar="M",
                     help="with --certify: Lanczos step budget (default 512)")
+    ap.add_argument("--refine", action="store_true",
+                    help="certified solve: refine the gathered iterate to "
+                         "criticality on the device, certify, and climb the "
+                         "rank staircase on a not-optimal verdict")
     args = ap.parse_args()
 
     from dpo_amd.io_g2o import load_dataset
@@ -87,7 +91,24 @@ def main():
             lg = PGOLogger(os.path.dirname(args.dump_trajectory) or ".")
             lg.log_trajectory(meas[0].d, n, T,
                               os.path.basename(args.dump_trajectory))
-    if args.certify:
+    if args.refine:
+        import torch
+        Xt = (drv.gather_lifted_iterate() if args.driver == "dist"
+              else drv._gather_global_x().reshape(-1, args.r))
+        if Xt is not None and rank == 0:
+            from dpo_amd.refine import certified_solve
+            kw = {}
+            if args.cert_basis is not None:
+                kw["basis_size"] = args.cert_basis
+            if args.cert_max_iters is not None:
+                kw["max_iters"] = args.cert_max_iters
+            t_cert = time.perf_counter()
+            stair = certified_solve(
+                meas, n, meas[0].d,
+                Xt.detach().to(torch.device(args.device)), certify_kw=kw)
+            out.update(stair.as_dict())
+            out["certified_solve_s"] = time.perf_counter() - t_cert
+    elif args.certify:
         import torch
         Xt = (drv.gather_lifted_iterate() if args.driver == "dist"
               else drv._gather_global_x().reshape(-1, args.r))

@@ -29,6 +29,10 @@ def main():
                          "of B vectors (basis memory N (B + 1) doubles)")
     ap.add_argument("--cert-max-iters", type=int, default=None, metavar="M",
                     help="with --certify: Lanczos step budget (default 512)")
+    ap.add_argument("--refine", action="store_true",
+                    help="certified solve: refine the result to criticality "
+                         "on the device, certify, and climb the rank "
+                         "staircase on a not-optimal verdict")
     args = ap.parse_args()
 
     from dpo_amd.agent import PGOAgent
@@ -56,10 +60,9 @@ def main():
         "grad_norm_opt": res.grad_norm_opt,
         "wall_s": wall,
     }
-    if args.certify:
+    if args.certify or args.refine:
         import numpy as np
         import torch
-        from dpo_amd.certify import certify_solution
         # r = d: the lifted iterate is the trajectory itself, transposed
         Xt = torch.from_numpy(np.ascontiguousarray(Topt.T)).to(
             torch.device(args.device))
@@ -68,8 +71,16 @@ def main():
             kw["basis_size"] = args.cert_basis
         if args.cert_max_iters is not None:
             kw["max_iters"] = args.cert_max_iters
-        cert = certify_solution(meas, n, d, Xt, **kw)
-        out.update(cert.as_dict())
+        if args.refine:
+            from dpo_amd.refine import certified_solve
+            t_cert = time.perf_counter()
+            stair = certified_solve(meas, n, d, Xt, certify_kw=kw)
+            out.update(stair.as_dict())
+            out["certified_solve_s"] = time.perf_counter() - t_cert
+        else:
+            from dpo_amd.certify import certify_solution
+            cert = certify_solution(meas, n, d, Xt, **kw)
+            out.update(cert.as_dict())
     print(json.dumps(out))
     if args.dump_trajectory:
         from dpo_amd.logger import PGOLogger
