@@ -1108,20 +1108,29 @@ class PGOAgent:
         self.Y = hb.polar_affine(self.X, self.V, None,
                                  1.0 - self.alpha, self.alpha, 0.0, self.d)
 
-    def _packed_nesterov_post(self, it: int) -> None:
+    def _packed_nesterov_post(self, do_optimization: bool) -> None:
+        """updateV and the restart test of iterate() (PGOAgent.cpp:690-694).
+        PackedBackend.select has advanced iteration_number for this round,
+        so the test is the reference's shouldRestart() verbatim."""
         from .ops import hip_backend as hb
         self.V = hb.polar_affine(self.V, self.X, self.Y,
                                  1.0, self.gamma, -self.gamma, self.d)
-        if (self.iteration_number + it + 1) % self.params.restart_interval == 0:
-            # periodic restart (PGOAgent.cpp:1040-1052)
-            self.X.copy_(self._XPrev_packed)
+        if self._should_restart():
+            self._packed_restart(do_optimization)
+
+    def _packed_restart(self, do_optimization: bool) -> None:
+        """restartNesterovAcceleration (PGOAgent.cpp:1040-1052): back to
+        XPrev; only an agent that optimizes this round re-solves from
+        there, against the plain (not aux) neighbor poses."""
+        self.X.copy_(self._XPrev_packed)
+        if do_optimization:
             self._dev_solver.round_solve(self.X, self._nbr_buffer,
                                          tol=self.params.inner_tol,
                                          Delta0=100.0)
-            self.V.copy_(self.X)
-            self.Y.copy_(self.X)
-            self.gamma = 0.0
-            self.alpha = 0.0
+        self.V.copy_(self.X)
+        self.Y.copy_(self.X)
+        self.gamma = 0.0
+        self.alpha = 0.0
 
     # ------------------------------------------------------------------
     # asynchronous optimization loop (PGOAgent.cpp:861-916)

@@ -156,6 +156,7 @@ class PackedBackend:
         self.fanout_eval = drv.selection in ("colored", "colored_greedy")
         self._gids = {}        # active set -> ctypes id array (group solve)
         self._active = []      # this round's local active agents
+        self._active_rbs = set()
         self._active_ids = None
 
     # -- boundary-pose exchange ------------------------------------------
@@ -179,7 +180,7 @@ class PackedBackend:
             blkv = flats[rk].view(-1, self.dh, self.r)
             target.index_copy_(0, dst_slots, blkv.index_select(0, src_idx))
 
-    def _exchange(self) -> None:
+    def _exchange(self, prepare: bool = True) -> None:
         """One all-gather per round. Accelerated mode computes the next
         Nesterov aux poses Y first and sends [X | Y] halves per rank in
         that same collective: nothing updates X or V between here and
@@ -188,8 +189,9 @@ class PackedBackend:
             self._scatter(self.comm.all_gather_flat(self._pack(),
                                                     self.sizes))
             return
-        for a in self.agents.values():
-            a._packed_nesterov_pre()
+        if prepare:
+            for a in self.agents.values():
+                a._packed_nesterov_pre()
         payload = torch.cat([self._pack(), self._pack(aux=True)])
         flats = self.comm.all_gather_flat(payload,
                                           [2 * s for s in self.sizes])
@@ -211,15 +213,18 @@ class PackedBackend:
         return buf
 
     def begin(self) -> None:
-        """Round-0 pre-exchange so G terms exist before the first solve."""
-        if self.accel:
-            for a in self.agents.values():
-                a.gamma = 0.0
-                a.alpha = 0.0
-        self._exchange()
+        """Round-0 pre-exchange so G terms exist before the first solve.
+        A fresh or restored accelerated state (gamma == 0) gets its first
+        gamma, alpha and Y here; after an earlier run() the last exchange
+        has prepared them already and the momentum carries on, as
+        iterate() carries it on the dict path."""
+        self._exchange(prepare=all(a.gamma == 0.0
+                                   for a in self.agents.values()))
 
     def reweight_due(self, round_counter: int) -> bool:
-        return self.robust and round_counter % self.gnc_period == 0
+        """shouldUpdateLoopClosureWeights (PGOAgent.cpp:1174-1179) with
+        the already advanced round number: rounds P-1, 2P-1, ..."""
+        return self.robust and (round_counter + 1) % self.gnc_period == 0
 
     def reweight(self) -> None:
         """GNC re-weighting round (reference iterate():
@@ -243,10 +248,25 @@ class PackedBackend:
         for a in self.agents.values():
             a._packed_rebuild_q()
             a.robust_cost.update()
+        if self.accel:
+            # initializeAcceleration (PGOAgent.cpp:663-666): momentum
+            # starts over on the re-weighted problem. The aux poses sent
+            # last round belong to the old momentum, so they are sent
+            # again (gamma = 0 gives alpha = 1 and Y = X).
+            for a in self.agents.values():
+                a.V.copy_(a.X)
+                a.gamma = 0.0
+                a.alpha = 0.0
+            self._exchange()
 
     def select(self, active) -> None:
         """Fix this round's active agents. Accelerated mode moves every
-        other agent to its aux point here, before the solves."""
+        other agent to its aux point here, before the solves. Called
+        once per round: it advances every agent's iteration_number, the
+        count iterate() keeps on the dict path (restart cadence)."""
+        for a in self.agents.values():
+            a.iteration_number += 1
+        self._active_rbs = set(active)
         if self.group_solve:
             key = tuple(active)
             ids = self._gids.get(key)
@@ -282,8 +302,8 @@ class PackedBackend:
 
     def exchange(self, it: int) -> None:
         if self.accel:
-            for a in self.agents.values():
-                a._packed_nesterov_post(it)
+            for rb, a in self.agents.items():
+                a._packed_nesterov_post(rb in self._active_rbs)
         self._exchange()
 
     def evaluate(self, row: Tensor) -> None:

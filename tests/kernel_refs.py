@@ -767,17 +767,20 @@ def small_problem(d: int, r: int, n: int, g: torch.Generator,
     return p, manifold_point(n, d, r, g)
 
 
-def eval_terms_ref(problem, X: Tensor):
+def eval_terms_ref(problem, X: Tensor, bG: Optional[Tensor] = None):
     """[f, 0.5 <X, G>, ||rgrad||^2] in fp64 on the CPU, with a bound for
     each from the sum-of-products rule: the spmm entries carry
     matmul_bound, the projection propagates it, and each scalar adds the
-    bound of its own final dot product."""
+    bound of its own final dot product. bG is an entry-wise bound on the
+    error already in the device's G (one assembled by a kernel)."""
     Q, d = problem.Q, problem.d
     G = problem._g()
     Qd = Q.to_dense()
     K = bsr_max_row_terms(Q) + 1
     A = Qd @ X + G
     bA = sop_bound(Qd.abs() @ X.abs() + G.abs(), K)
+    if bG is not None:
+        bA = bA + bG
     f = 0.5 * float(((Qd @ X) * X).sum()) + float((G * X).sum())
     xg = 0.5 * float((X * G).sum())
     P = cpu_ref.tangent_project(X, A, d)
@@ -787,6 +790,276 @@ def eval_terms_ref(problem, X: Tensor):
     b_f = float((bA * X.abs()).sum()) + float(sop_bound(
         (A.abs() * X.abs()).sum() + (G.abs() * X.abs()).sum(), T))
     b_xg = float(sop_bound((G.abs() * X.abs()).sum(), T))
+    if bG is not None:     # b_f has it through bA
+        b_xg += 0.5 * float((bG * X.abs()).sum())
     b_gn2 = float((2.0 * P.abs() * bP + bP * bP).sum()) + float(
         sop_bound((P * P).sum(), T))
     return (np.array([f, xg, gn2]), np.array([b_f, b_xg, b_gn2]), P, bP)
+
+
+# ---------------------------------------------------------------------
+# packed round loop (tests/test_packed_rounds*.py)
+# ---------------------------------------------------------------------
+class StubComm:
+    """rank `rank` of `world_size` with no process group behind it. The
+    driver and PackedBackend constructors only read the two numbers; the
+    tests hand the gathered payloads to _scatter themselves, so a
+    collective reached by accident is an error, not a hang."""
+
+    def __init__(self, rank: int, world_size: int):
+        self.rank, self.world_size = rank, world_size
+
+    def all_gather_flat(self, local, sizes):
+        raise AssertionError("collective on a stub communicator")
+
+    all_reduce_sum_ = barrier = all_gather_flat
+
+
+def interleaved_partition(num_poses: int, num_robots: int, run: int = 3):
+    """pose g -> robot (g // run) % num_robots: every robot owns many
+    short runs of the trajectory, so local order, public-pose indices and
+    neighbour slot order all differ from the contiguous split."""
+    return [(g // run) % num_robots for g in range(num_poses)]
+
+
+def agent_edge_index(p1, p2, part, rb: int):
+    """Global measurement indices of agent rb's (odometry, private,
+    shared) edges, in the order the agent stores them: input order within
+    each class; odometry is a same-robot edge between consecutive global
+    poses."""
+    part = np.asarray(part)
+    p1, p2 = np.asarray(p1), np.asarray(p2)
+    r1, r2 = part[p1], part[p2]
+    same = r1 == r2
+    odo = same & (p1 + 1 == p2)
+    return (np.nonzero(odo & (r1 == rb))[0],
+            np.nonzero(same & ~odo & (r1 == rb))[0],
+            np.nonzero(~same & ((r1 == rb) | (r2 == rb)))[0])
+
+
+def central_eval_ref(meas, n: int, d: int, Xg: Tensor, weights=None):
+    """(<QX, X>, ||rgrad||^2) of the centralized problem at the global
+    iterate Xg, fp64 on the CPU, each with the sum-of-products bound of
+    this reference's own arithmetic."""
+    from dpo_amd.quadratic import assemble_connection_laplacian
+    Q = assemble_connection_laplacian(meas, n, d, weights)
+    Qd = Q.to_dense()
+    K = bsr_max_row_terms(Q) + 1
+    A = Qd @ Xg
+    bA = sop_bound(Qd.abs() @ Xg.abs(), K)
+    T = Xg.numel()
+    cost = float((A * Xg).sum())
+    b_cost = float((bA * Xg.abs()).sum()) + float(
+        sop_bound((A.abs() * Xg.abs()).sum(), T))
+    P = cpu_ref.tangent_project(Xg, A, d)
+    bP = tangent_project_bound(Xg, A, d, bA)
+    gn2 = float((P * P).sum())
+    b_gn2 = float((2.0 * P.abs() * bP + bP * bP).sum()) + float(
+        sop_bound((P * P).sum(), T))
+    return cost, gn2, b_cost, b_gn2
+
+
+def agent_eval_ref(agent, nbr: Tensor, weights: Tensor):
+    """[f, 0.5 <X, G>, ||rgrad||^2] of one agent and their bounds
+    (eval_terms_ref), on the agent's own Q assembled on the CPU from
+    `weights` (odometry | private | shared) and the G assembled on the
+    CPU from the neighbour buffer `nbr` (n_slots, dh, r). G is a
+    scatter-add of dh-term products, so it carries its own bound from the
+    abs() copies of E0 and nbr."""
+    from types import SimpleNamespace
+    from dpo_amd.quadratic import GAssembler
+    X = agent.X.detach().cpu()
+    weights = weights.detach().cpu()
+    Q = agent._q_assembler.assemble(weights.clone())
+    Q = BSRMatrix(Q.n, Q.dh, Q.row_ptr.clone(), Q.col_idx.clone(),
+                  Q.vals.clone())
+    ga = agent._g_assembler
+    nsh = ga.E0.shape[0]
+    wsh = weights[weights.numel() - nsh:]
+    if nsh:
+        G = ga.assemble(nbr.cpu(), wsh, agent.r)
+        gabs = GAssembler.__new__(GAssembler)
+        gabs.n, gabs.d = ga.n, ga.d
+        gabs.E0, gabs.local_pose, gabs.nbr_slot = \
+            ga.E0.abs(), ga.local_pose, ga.nbr_slot
+        deg = int(torch.bincount(ga.local_pose).max())
+        bG = sop_bound(gabs.assemble(nbr.cpu().abs(), wsh.abs(),
+                                     agent.r).abs(), deg * ga.E0.shape[1] + 1)
+    else:
+        G = torch.zeros_like(X)
+        bG = torch.zeros_like(X)
+    prob = SimpleNamespace(Q=Q, d=agent.d, _g=lambda: G)
+    return eval_terms_ref(prob, X, bG)[:2]
+
+
+def schedule_probe(drv):
+    """Instrument a DistributedRBCDDriver (either backend) and return the
+    log its later run() calls fill: per agent the 1-based round numbers,
+    counted over the driver's life, of every Nesterov restart and every
+    GNC re-weighting, and gamma as each solve phase sees it. The round
+    number is counted by wrapping reweight_due(), the first call of every
+    round on whichever backend run() picks."""
+    log = {"round": 0, "restart": {}, "reweight": {}, "gamma": {}}
+    for rb, a in drv.local_agents.items():
+        for k in ("restart", "reweight", "gamma"):
+            log[k][rb] = []
+
+        def wrap(name, key, a=a, rb=rb):
+            inner = getattr(a, name)
+
+            def f(*args, **kw):
+                log[key][rb].append(log["round"])
+                return inner(*args, **kw)
+            setattr(a, name, f)
+        wrap("_restart_nesterov", "restart")          # dict path
+        wrap("_packed_restart", "restart")            # packed path
+        wrap("update_loop_closures_weights", "reweight")
+        wrap("_packed_update_weights", "reweight")
+    make = drv._backend
+
+    def backend():
+        b = make()
+        if getattr(b, "_probed", False):
+            return b
+        b._probed = True
+        due, solve = b.reweight_due, b.solve
+
+        def due_(round_counter):
+            log["round"] += 1
+            return due(round_counter)
+
+        def solve_():
+            # the dict path updates gamma inside iterate(): record what
+            # _update_x sees; the packed path has it ready before solve()
+            if drv.acceleration and hasattr(b, "rank_X"):
+                for rb, a in drv.local_agents.items():
+                    log["gamma"][rb].append(a.gamma)
+            return solve()
+        b.reweight_due, b.solve = due_, solve_
+        return b
+    drv._backend = backend
+    if drv.acceleration:
+        for rb, a in drv.local_agents.items():
+            def ux(do_opt, acceleration, a=a, rb=rb, inner=a._update_x):
+                if acceleration:
+                    log["gamma"][rb].append(a.gamma)
+                return inner(do_opt, acceleration)
+            a._update_x = ux
+    return log
+
+
+SCHED_RESTART, SCHED_GNC = 5, 4      # restart_interval, inner iters
+SCHED_RUNS = (7, 6)                  # two run() calls, then a restored one
+
+
+def schedule_model(rounds: int, num_robots: int, accel: bool, robust: bool):
+    """The reference's cadence (PGOAgent.cpp iterate(), shouldRestart(),
+    shouldUpdateLoopClosureWeights()): round k = 1, 2, ... re-weights at
+    its start when (k + 1) % SCHED_GNC == 0, which also resets gamma, and
+    restarts at its end when (k + 1) % SCHED_RESTART == 0. Returns
+    (restart rounds, re-weighting rounds, gamma seen by each solve)."""
+    restart, reweight, gammas = [], [], []
+    gamma, K = 0.0, num_robots
+    for k in range(1, rounds + 1):
+        if robust and (k + 1) % SCHED_GNC == 0:
+            reweight.append(k)
+            gamma = 0.0
+        if accel:
+            gamma = (1 + math.sqrt(1 + 4 * K * K * gamma * gamma)) / (2 * K)
+            gammas.append(gamma)
+            if (k + 1) % SCHED_RESTART == 0:
+                restart.append(k)
+                gamma = 0.0
+    return restart, reweight, gammas
+
+
+def run_schedule(drv):
+    """Two consecutive run() calls and one after restore_initial_state()
+    on a probed driver: [(restart, reweight, gamma) per agent] for the
+    first two together and for the restored one."""
+    for a in drv.local_agents.values():
+        a.params.restart_interval = SCHED_RESTART
+        a.params.robust_opt_inner_iters = SCHED_GNC
+    log = schedule_probe(drv)
+    drv.snapshot_initial_state()
+
+    def take():
+        out = {rb: (log["restart"][rb][:], log["reweight"][rb][:],
+                    log["gamma"][rb][:]) for rb in drv.local_agents}
+        for k in ("restart", "reweight", "gamma"):
+            for v in log[k].values():
+                v.clear()
+        log["round"] = 0
+        return out
+    for n in SCHED_RUNS:
+        res = drv.run(max_iters=n, gradnorm_tol=0.0)
+        assert res.iterations == n
+    first = take()
+    drv.restore_initial_state()
+    drv.run(max_iters=SCHED_RUNS[1], gradnorm_tol=0.0)
+    return first, take()
+
+
+def check_schedule(got, rounds: int, num_robots: int, accel: bool,
+                   robust: bool):
+    want = schedule_model(rounds, num_robots, accel, robust)
+    assert sorted(got) == list(range(num_robots))
+    for rb, lists in got.items():
+        assert lists == want, (rb, lists, want)
+
+
+# GNC fixture: grid3d_soa side 4, 30 % planted outliers, odometry
+# dead-reckoning iterate (what the robust drivers start from)
+GNC_SIDE, GNC_OUTLIERS, GNC_SEED = 4, 0.3, 5
+
+
+def gnc_fixture():
+    """(MeasurementArray, n, global lifted iterate (r, dh n) at r = 5)."""
+    from dpo_amd.manifold import lifting_matrix
+    from dpo_amd.measurements import odometry_initialization_array
+    from dpo_amd.synthetic import grid3d_soa
+    ma, n = grid3d_soa(side=GNC_SIDE, outlier_prob=GNC_OUTLIERS,
+                       seed=GNC_SEED)
+    T = odometry_initialization_array(3, n, ma.select(ma.p1 + 1 == ma.p2))
+    return ma, n, lifting_matrix(3, 5) @ T
+
+
+def set_global_iterate(drv, Xg: np.ndarray) -> None:
+    """set_x every local agent to its poses of the global iterate."""
+    dh = drv.dh
+    for rb, a in drv.local_agents.items():
+        cols = np.concatenate([
+            np.arange(dh) + dh * drv.pose_to_index[(rb, i)]
+            for i in range(drv.pose_counts[rb])])
+        a.set_x(np.ascontiguousarray(Xg[:, cols]))
+
+
+def gnc_edge_residuals(ma, Xg: np.ndarray, d: int = 3):
+    """r^2 of every measurement at the global iterate and the
+    sum-of-products bound of that number: each of the dh r residual
+    entries is a (d + 1)-term sum, squared and added up."""
+    dh = d + 1
+    r = Xg.shape[0]
+    P = np.ascontiguousarray(Xg.T).reshape(-1, dh, r)
+    P1, P2 = P[ma.p1], P[ma.p2]
+    r_sq = gnc_residual_sq(P1, P2, ma.R, ma.t, ma.kappa, ma.tau, d)
+    A1, A2 = np.abs(P1), np.abs(P2)
+    A1[:, d, :] *= -1.0     # p2 - p1 - t^T Y1 -> |p2| + |p1| + |t|^T |Y1|
+    A2[:, :d, :] *= -1.0    # R^T Y1 - Y2      -> |R|^T |Y1| + |Y2|
+    r_abs = gnc_residual_sq(A1, A2, np.abs(ma.R), -np.abs(ma.t), ma.kappa,
+                            ma.tau, d)
+    return r_sq, sop_bound(r_abs, 2 * (d + 1) + dh * r)
+
+
+def gnc_near_threshold(r_sq, bound, mu: float, barc: float) -> np.ndarray:
+    """Edges whose r^2 is within its bound of a GNC-TLS threshold."""
+    lower = mu / (mu + 1.0) * barc ** 2
+    upper = (mu + 1.0) / mu * barc ** 2
+    return (np.abs(r_sq - lower) <= bound) | (np.abs(r_sq - upper) <= bound)
+
+
+def nbr_from_dict(agent) -> Tensor:
+    """The neighbour buffer (n_slots, dh, r) the dict path would build."""
+    return torch.from_numpy(np.stack(
+        [agent.neighbor_pose_dict[pid].T
+         for pid in agent._nbr_slot_order]))
