@@ -735,26 +735,42 @@ class PGOAgent:
                 return False
         return True
 
-    def get_trajectory_in_local_frame(self) -> Optional[np.ndarray]:
+    def get_trajectory_in_local_frame(self, device: bool = False
+                                      ) -> Optional[np.ndarray]:
         """Round to SE(d) in the frame of the agent's first pose
-        (PGOAgent.cpp:481-498)."""
+        (PGOAgent.cpp:481-498). `device=True` rounds through the op
+        backend on X's own device (HIP kernels on a GPU, no per-pose host
+        loop, X not copied to the host); the default is the host loop."""
         if self.state != PGOAgentState.INITIALIZED:
             return None
         with self._lock:
+            if device:
+                anchor = self.X[:self.dh].detach().cpu().numpy().T
+                return self._round_trajectory_device(anchor)
             X = self.X.cpu().numpy().T  # (r, N)
             return self._round_trajectory(X, X[:, :self.d],
                                           X[:, self.d])
 
-    def get_trajectory_in_global_frame(self) -> Optional[np.ndarray]:
+    def get_trajectory_in_global_frame(self, device: bool = False
+                                       ) -> Optional[np.ndarray]:
+        """Round to SE(d) in the frame of the global anchor; `device` as
+        in `get_trajectory_in_local_frame`."""
         if self.global_anchor is None:
             return None
         if self.state != PGOAgentState.INITIALIZED:
             return None
         with self._lock:
+            if device:
+                return self._round_trajectory_device(self.global_anchor)
             X = self.X.cpu().numpy().T
             anchor = self.global_anchor
             return self._round_trajectory(X, anchor[:, :self.d],
                                           anchor[:, self.d])
+
+    def _round_trajectory_device(self, anchor: np.ndarray) -> np.ndarray:
+        from .rounding import round_anchor
+        traj, _ = round_anchor(self.X, self.d, anchor)
+        return np.ascontiguousarray(traj.cpu().numpy())
 
     def _round_trajectory(self, X: np.ndarray, Ya: np.ndarray,
                           pa: np.ndarray) -> np.ndarray:

@@ -642,10 +642,14 @@ class DistributedRBCDDriver:
             a.iteration_number = 0
         self._round_counter = 0
 
-    def gather_final_trajectory(self):
+    def gather_final_trajectory(self, device: bool = False):
         """Rounded global trajectory (d, (d+1) n) on rank 0 (reference
         PartitionInitial.cpp:329-335 output). Returns None on other
-        ranks."""
+        ranks. `device=True` rounds every agent on its own device
+        (`dpo_amd.rounding.round_anchor`) and scatters with one
+        index_copy_ per agent; the default host path is unchanged."""
+        if device:
+            return self._gather_final_trajectory_device()
         self._sync_anchor()
         dh = self.dh
         buf = torch.zeros(self.n_global, self.d, dh, dtype=torch.float64)
@@ -663,6 +667,29 @@ class DistributedRBCDDriver:
         return np.ascontiguousarray(
             buf.numpy().transpose(1, 0, 2).reshape(self.d,
                                                    self.n_global * dh))
+
+    def _gather_final_trajectory_device(self):
+        from .rounding import round_anchor
+        self._sync_anchor()
+        dh, d = self.dh, self.d
+        dev = self._packed.dev if self._packed is not None else "cpu"
+        buf = torch.zeros(self.n_global, dh, d, dtype=torch.float64,
+                          device=dev)
+        for rb, a in self.local_agents.items():
+            if a.global_anchor is None or \
+                    a.state != PGOAgentState.INITIALIZED:
+                continue
+            _, Xr = round_anchor(a.X, d, a.global_anchor)
+            idx = torch.tensor([self.pose_to_index[(rb, i)]
+                                for i in range(a.n)], dtype=torch.int64,
+                               device=Xr.device)
+            buf.index_copy_(0, idx.to(buf.device),
+                            Xr.view(a.n, dh, d).to(buf.device))
+        self.comm.all_reduce_sum_(buf.view(-1))
+        if self.comm.rank != 0:
+            return None
+        return np.ascontiguousarray(
+            buf.view(self.n_global * dh, d).T.cpu().numpy())
 
     def gather_lifted_iterate(self):
         """Global lifted iterate Xt (n_global (d+1), r) on rank 0, pose

@@ -441,3 +441,79 @@ def refine_candidate(Q, ws: RefineWorkspace, ctl: Tensor, d: int) -> None:
     ctl[RF_STATUS] = RS_HEAD
     if acc:
         ws.X.copy_(ws.Xp)
+
+
+# ---------------------------------------------------------------------
+# rounding: the lifted iterate to SE(d) (docs/DESIGN.md §19). Batched
+# torch, no loop over poses; the HIP kernels use another algorithm
+# (closed form / Jacobi on the Davenport matrix) for the same maximiser.
+# ---------------------------------------------------------------------
+def project_to_rotations(B: Tensor) -> Tensor:
+    """argmax_{R in SO(d)} tr(R^T B) for every block of B (n, d, d):
+    U V^T of the SVD with the determinant fix on U's last column."""
+    U, _, Vh = torch.linalg.svd(B)
+    neg = torch.linalg.det(U) * torch.linalg.det(Vh) < 0
+    U = U.clone()
+    U[neg, :, -1] *= -1.0
+    return torch.bmm(U, Vh)
+
+
+def _round_blocks(Xt: Tensor, d: int, U: Tensor):
+    """U^T Y_i (n, d, d) and U^T p_i (n, d)."""
+    r = Xt.shape[1]
+    cert_check_shape(d, r)
+    assert U.shape == (r, d)
+    Xb = _pose_view(Xt, d)
+    P = Xb @ U.to(Xt.dtype)                 # (n, d+1, d), row a = (U^T y_a)^T
+    return P[:, :d, :].transpose(1, 2), P[:, d, :]
+
+
+def round_gram(Xt: Tensor, d: int) -> Tensor:
+    """S = sum_i Y_i Y_i^T (r, r) over the rotation rows."""
+    cert_check_shape(d, Xt.shape[1])
+    Yt = _pose_view(Xt, d)[:, :d, :].reshape(-1, Xt.shape[1])
+    return Yt.T @ Yt
+
+
+def round_poses(Xt: Tensor, d: int, U: Tensor, t0: Tensor,
+                flip: bool = False):
+    """(traj (d, n (d+1)), Xr (n (d+1), d)): R_i = the SO(d) projection of
+    U^T Y_i, t_i = U^T p_i - t0; `flip` negates U's last column."""
+    if flip:
+        U = U.clone()
+        U[:, -1] *= -1.0
+    B, t = _round_blocks(Xt, d, U)
+    n = B.shape[0]
+    out = torch.empty(n, d + 1, d, dtype=Xt.dtype)
+    out[:, :d, :] = project_to_rotations(B).transpose(1, 2)
+    out[:, d, :] = t - t0.to(Xt.dtype)
+    Xr = out.view(n * (d + 1), d)
+    return Xr.T.contiguous(), Xr
+
+
+def round_reflections(Xt: Tensor, d: int, U: Tensor) -> Tensor:
+    """1-element int32 tensor: poses with det(U^T Y_i) < 0."""
+    B, _ = _round_blocks(Xt, d, U)
+    neg = torch.linalg.slogdet(B)[0] < 0
+    return neg.sum().to(torch.int32).reshape(1)
+
+
+def round_gauge(Xr: Tensor, traj: Tensor, d: int, anchor_pose: int) -> None:
+    """In place on both layouts: R_i <- R_a^T R_i, t_i <- R_a^T (t_i -
+    t_a) for a = anchor_pose."""
+    cert_check_shape(d, d)
+    dh = d + 1
+    Xb = Xr.view(-1, dh, d)
+    A = Xb[anchor_pose].clone()
+    Xb[:, d, :] -= A[d]
+    Ra = A[:d].T                            # Xt layout holds R_a^T
+    Xb.copy_(Xb @ Ra)                       # rows v^T -> (R_a^T v)^T
+    traj.copy_(Xr.T)
+
+
+def round_cost(Q, X: Tensor, G: Optional[Tensor] = None) -> Tensor:
+    """1-element tensor f(X) = 0.5 <Q X, X> + <X, G>."""
+    f = 0.5 * (torch.sparse.mm(Q.to_scalar_csr(), X) * X).sum()
+    if G is not None:
+        f = f + (X * G).sum()
+    return f.reshape(1)

@@ -4143,3 +4143,387 @@ void dpo_refine_stage(int stage, const int* row_ptr, const int* col_idx,
 int dpo_refine_ctrl_size() { return RF_SIZE; }
 
 }  // extern "C"
+
+// =====================================================================
+// Rounding: the lifted iterate to SE(d) on the device (docs/DESIGN.md
+// §19). Purely additive; one thread per pose, everything in registers,
+// the launch geometry of k_polar_affine (per-pose maps) and
+// k_cert_lambda (reductions).
+//
+//   k_round_gram         S = sum_i Y_i Y_i^T (r x r) over the rotation
+//                        rows, per-block partials in a fixed order
+//   k_round_gram_finish  sums the <= CERT_MAX_PART partials per entry
+//   k_round_poses        B_i = U^T Y_i, R_i = argmax_{SO(d)} tr(R^T B_i),
+//                        t_i = U^T p_i - t0, in both output layouts
+//   k_round_reflections  number of poses with det(U^T Y_i) < 0
+//   k_round_gauge        R_i <- R_a^T R_i, t_i <- R_a^T (t_i - t_a)
+//
+// Reductions follow the certificate's rule: one partial
+// per block and entry, summed by a later launch in a fixed order; no
+// floating-point atomics, so S is bitwise run-to-run reproducible.
+//
+// Projection onto SO(d). The block is first scaled by an exact power of
+// two so that its largest entry lies in [1, 2): nothing is squared at
+// the input's scale. d = 2: tr(R^T B) = cos(a) (B00 + B11) + sin(a)
+// (B10 - B01), maximised in closed form. d = 3: tr(R(q)^T B) = q^T K q
+// for the 4 x 4 symmetric Davenport matrix K, which is LINEAR in B; its
+// top eigenvector comes from a fixed number of cyclic Jacobi sweeps and
+// gives the rotation as a unit quaternion. The eigenvalue gap of K is
+// 2 (sigma_2 + sign(det B) sigma_3), the conditioning of the problem
+// itself; det B < 0, repeated singular values and singular blocks need
+// no special case (any top eigenvector is a maximiser; K = 0 gives the
+// identity).
+// =====================================================================
+#define ROUND_JACOBI_SWEEPS 8
+#define ROUND_MAX_GRAM (DPO_MAX_R * (DPO_MAX_R + 1) / 2)
+
+template <int D>
+__device__ __forceinline__ void round_normalize(double (&B)[D][D]) {
+  double m = 0.0;
+  #pragma unroll
+  for (int a = 0; a < D; ++a)
+    #pragma unroll
+    for (int b = 0; b < D; ++b) m = fmax(m, fabs(B[a][b]));
+  if (m > 0.0 && m <= 1.7976931348623157e308) {
+    const int e = -ilogb(m);
+    #pragma unroll
+    for (int a = 0; a < D; ++a)
+      #pragma unroll
+      for (int b = 0; b < D; ++b) B[a][b] = scalbn(B[a][b], e);
+  }
+}
+
+// determinant of a block already normalised by round_normalize
+__device__ __forceinline__ double round_det(const double (&B)[2][2]) {
+  return B[0][0] * B[1][1] - B[0][1] * B[1][0];
+}
+__device__ __forceinline__ double round_det(const double (&B)[3][3]) {
+  return B[0][0] * (B[1][1] * B[2][2] - B[1][2] * B[2][1])
+       - B[0][1] * (B[1][0] * B[2][2] - B[1][2] * B[2][0])
+       + B[0][2] * (B[1][0] * B[2][1] - B[1][1] * B[2][0]);
+}
+
+__device__ __forceinline__ void round_project(double (&B)[2][2],
+                                              double (&Rm)[2][2]) {
+  round_normalize<2>(B);
+  const double x = B[0][0] + B[1][1], y = B[1][0] - B[0][1];
+  const double n2 = x * x + y * y;
+  const bool ok = n2 > 0.0;
+  const double inv = 1.0 / sqrt(ok ? n2 : 1.0);
+  const double c = ok ? x * inv : 1.0, s = ok ? y * inv : 0.0;
+  Rm[0][0] = c; Rm[0][1] = -s;
+  Rm[1][0] = s; Rm[1][1] = c;
+}
+
+__device__ __forceinline__ void round_project(double (&B)[3][3],
+                                              double (&Rm)[3][3]) {
+  round_normalize<3>(B);
+  // q = (w, x, y, z); K from the expansion of sum_ij R(q)_ij B_ij
+  double A[4][4], V[4][4];
+  A[0][0] = B[0][0] + B[1][1] + B[2][2];
+  A[1][1] = B[0][0] - B[1][1] - B[2][2];
+  A[2][2] = -B[0][0] + B[1][1] - B[2][2];
+  A[3][3] = -B[0][0] - B[1][1] + B[2][2];
+  A[0][1] = A[1][0] = B[2][1] - B[1][2];
+  A[0][2] = A[2][0] = B[0][2] - B[2][0];
+  A[0][3] = A[3][0] = B[1][0] - B[0][1];
+  A[1][2] = A[2][1] = B[0][1] + B[1][0];
+  A[1][3] = A[3][1] = B[0][2] + B[2][0];
+  A[2][3] = A[3][2] = B[1][2] + B[2][1];
+  #pragma unroll
+  for (int a = 0; a < 4; ++a)
+    #pragma unroll
+    for (int b = 0; b < 4; ++b) V[a][b] = (a == b) ? 1.0 : 0.0;
+  for (int sweep = 0; sweep < ROUND_JACOBI_SWEEPS; ++sweep) {
+    #pragma unroll
+    for (int p = 0; p < 3; ++p)
+      #pragma unroll
+      for (int q = p + 1; q < 4; ++q) {
+        const double apq = A[p][q];
+        const bool nz = apq != 0.0;
+        const double theta = (A[q][q] - A[p][p]) / (2.0 * (nz ? apq : 1.0));
+        // theta^2 may overflow to inf: t = 0 then, the right limit
+        const double tt = copysign(1.0, theta)
+                        / (fabs(theta) + sqrt(theta * theta + 1.0));
+        const double t = nz ? tt : 0.0;
+        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+        A[p][p] -= t * apq;
+        A[q][q] += t * apq;
+        A[p][q] = A[q][p] = 0.0;
+        #pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          if (k != p && k != q) {
+            const double akp = A[k][p], akq = A[k][q];
+            A[k][p] = A[p][k] = c * akp - s * akq;
+            A[k][q] = A[q][k] = s * akp + c * akq;
+          }
+          const double vkp = V[k][p], vkq = V[k][q];
+          V[k][p] = c * vkp - s * vkq;
+          V[k][q] = s * vkp + c * vkq;
+        }
+      }
+  }
+  // eigenvector of the largest eigenvalue (ties: the first)
+  double lam = A[0][0];
+  double q[4] = {V[0][0], V[1][0], V[2][0], V[3][0]};
+  #pragma unroll
+  for (int j = 1; j < 4; ++j) {
+    const bool up = A[j][j] > lam;
+    lam = up ? A[j][j] : lam;
+    #pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = up ? V[k][j] : q[k];
+  }
+  const double inv = 1.0 / sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2]
+                                + q[3] * q[3]);
+  const double w = q[0] * inv, x = q[1] * inv, y = q[2] * inv,
+               z = q[3] * inv;
+  Rm[0][0] = 1.0 - 2.0 * (y * y + z * z);
+  Rm[0][1] = 2.0 * (x * y - w * z);
+  Rm[0][2] = 2.0 * (x * z + w * y);
+  Rm[1][0] = 2.0 * (x * y + w * z);
+  Rm[1][1] = 1.0 - 2.0 * (x * x + z * z);
+  Rm[1][2] = 2.0 * (y * z - w * x);
+  Rm[2][0] = 2.0 * (x * z - w * y);
+  Rm[2][1] = 2.0 * (y * z + w * x);
+  Rm[2][2] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+// B[c][a] = sum_k sg_c U[k][c] Y[k][a] of pose block Xi (Xt layout:
+// Xi[a * R + k] = Y[k][a]); U is (R, D) row-major, sg_c = -1 on the
+// last column when flip is set
+template <int D, int R>
+__device__ __forceinline__ void round_block(const double* __restrict__ Xi,
+                                            const double* __restrict__ U,
+                                            int flip, double (&B)[D][D]) {
+  #pragma unroll
+  for (int c = 0; c < D; ++c) {
+    const double sg = (flip && c == D - 1) ? -1.0 : 1.0;
+    #pragma unroll
+    for (int a = 0; a < D; ++a) {
+      double s = 0.0;
+      #pragma unroll
+      for (int k = 0; k < R; ++k) s = fma(U[k * D + c], Xi[a * R + k], s);
+      B[c][a] = sg * s;
+    }
+  }
+}
+
+template <int D, int R>
+__global__ void __launch_bounds__(CERT_BS)
+k_round_gram(const double* __restrict__ X, double* __restrict__ gpart,
+             int n) {
+  constexpr int dh = D + 1;
+  constexpr int NE = R * (R + 1) / 2;
+  double acc[NE];
+  #pragma unroll
+  for (int e = 0; e < NE; ++e) acc[e] = 0.0;
+  for (int i = blockIdx.x * CERT_BS + threadIdx.x; i < n;
+       i += gridDim.x * CERT_BS) {
+    const double* Xi = X + (size_t)i * dh * R;
+    double Y[D][R];
+    #pragma unroll
+    for (int a = 0; a < D; ++a)
+      #pragma unroll
+      for (int k = 0; k < R; ++k) Y[a][k] = Xi[a * R + k];
+    int e = 0;
+    #pragma unroll
+    for (int k = 0; k < R; ++k)
+      #pragma unroll
+      for (int l = k; l < R; ++l, ++e) {
+        double s = acc[e];
+        #pragma unroll
+        for (int a = 0; a < D; ++a) s = fma(Y[a][k], Y[a][l], s);
+        acc[e] = s;
+      }
+  }
+  #pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    const double s = cert_block_sum(acc[e]);
+    if (threadIdx.x == 0) gpart[e * CERT_MAX_PART + blockIdx.x] = s;
+  }
+}
+
+// S (r, r) row-major, both triangles, from the per-block partials
+__global__ void __launch_bounds__(CERT_BS)
+k_round_gram_finish(const double* __restrict__ gpart, int npart, int r,
+                    double* __restrict__ S) {
+  int e = 0;
+  for (int k = 0; k < r; ++k)
+    for (int l = k; l < r; ++l, ++e) {
+      const double s = cert_sum_partials(gpart + e * CERT_MAX_PART, npart);
+      if (threadIdx.x == 0) {
+        S[k * r + l] = s;
+        S[l * r + k] = s;
+      }
+    }
+}
+
+template <int D, int R>
+__global__ void k_round_poses(const double* __restrict__ X,
+                              const double* __restrict__ U,
+                              const double* __restrict__ t0, int flip,
+                              double* __restrict__ traj,
+                              double* __restrict__ Xr, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr int dh = D + 1;
+  const double* Xi = X + (size_t)i * dh * R;
+  double B[D][D], Rm[D][D], t[D];
+  round_block<D, R>(Xi, U, flip, B);
+  #pragma unroll
+  for (int c = 0; c < D; ++c) {
+    const double sg = (flip && c == D - 1) ? -1.0 : 1.0;
+    double s = 0.0;
+    #pragma unroll
+    for (int k = 0; k < R; ++k) s = fma(U[k * D + c], Xi[D * R + k], s);
+    t[c] = sg * s - t0[c];
+  }
+  round_project(B, Rm);
+  const size_t ld = (size_t)n * dh;
+  double* Ti = traj + (size_t)i * dh;
+  double* Xo = Xr + (size_t)i * dh * D;
+  #pragma unroll
+  for (int c = 0; c < D; ++c) {
+    #pragma unroll
+    for (int a = 0; a < D; ++a) {
+      Ti[c * ld + a] = Rm[c][a];
+      Xo[a * D + c] = Rm[c][a];
+    }
+    Ti[c * ld + D] = t[c];
+    Xo[D * D + c] = t[c];
+  }
+}
+
+// fixed-order block sum of an int (blockDim.x == CERT_BS)
+__device__ __forceinline__ int round_block_count(int v) {
+  __shared__ int shc[CERT_BS / 64];
+  #pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) shc[threadIdx.x >> 6] = v;
+  __syncthreads();
+  int s = shc[0];
+  #pragma unroll
+  for (int w = 1; w < CERT_BS / 64; ++w) s += shc[w];
+  __syncthreads();
+  return s;
+}
+
+template <int D, int R>
+__global__ void __launch_bounds__(CERT_BS)
+k_round_reflections(const double* __restrict__ X,
+                    const double* __restrict__ U, int* __restrict__ ipart,
+                    int n) {
+  constexpr int dh = D + 1;
+  int cnt = 0;
+  for (int i = blockIdx.x * CERT_BS + threadIdx.x; i < n;
+       i += gridDim.x * CERT_BS) {
+    double B[D][D];
+    round_block<D, R>(X + (size_t)i * dh * R, U, 0, B);
+    round_normalize<D>(B);
+    cnt += round_det(B) < 0.0 ? 1 : 0;
+  }
+  const int s = round_block_count(cnt);
+  if (threadIdx.x == 0) ipart[blockIdx.x] = s;
+}
+
+__global__ void __launch_bounds__(CERT_BS)
+k_round_count_finish(const int* __restrict__ ipart, int npart,
+                     int* __restrict__ count) {
+  const int t = threadIdx.x;
+  const int s = round_block_count(t < npart ? ipart[t] : 0);
+  if (t == 0) count[0] = s;
+}
+
+// anchor: one pose block in the Xt layout at rank d ((d + 1) x d: rows
+// a < d hold R_a[:, a], row d holds t_a), in a buffer of its own (the
+// pose it was copied from is overwritten like every other)
+template <int D>
+__global__ void k_round_gauge(double* __restrict__ Xr,
+                              double* __restrict__ traj,
+                              const double* __restrict__ anchor, int n) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  constexpr int dh = D + 1;
+  double* Xo = Xr + (size_t)i * dh * D;
+  double P[dh][D];
+  #pragma unroll
+  for (int a = 0; a < dh; ++a)
+    #pragma unroll
+    for (int k = 0; k < D; ++k) P[a][k] = Xo[a * D + k];
+  #pragma unroll
+  for (int k = 0; k < D; ++k) P[D][k] -= anchor[D * D + k];
+  const size_t ld = (size_t)n * dh;
+  double* Ti = traj + (size_t)i * dh;
+  #pragma unroll
+  for (int a = 0; a < dh; ++a)
+    #pragma unroll
+    for (int c = 0; c < D; ++c) {
+      // (R_a^T v)[c] = sum_k R_a[k][c] v[k], R_a[k][c] = anchor[c * D + k]
+      double s = 0.0;
+      #pragma unroll
+      for (int k = 0; k < D; ++k) s = fma(anchor[c * D + k], P[a][k], s);
+      Xo[a * D + c] = s;
+      Ti[c * ld + a] = s;
+    }
+}
+
+extern "C" {
+
+// S (r, r) = sum_i Y_i Y_i^T. gpart: dpo_round_gram_part() scratch
+// doubles. Nothing synchronises.
+void dpo_round_gram(const double* X, double* S, double* gpart, int n, int d,
+                    int r, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int g = cert_grid(n);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_round_gram<Dc, Rc>), dim3(g), dim3(CERT_BS), 0,
+                           s, X, gpart, n);
+      }))
+    dpo_bad_shape(d, r);
+  hipLaunchKernelGGL(k_round_gram_finish, dim3(1), dim3(CERT_BS), 0, s,
+                     (const double*)gpart, g, r, S);
+}
+
+int dpo_round_gram_part() { return ROUND_MAX_GRAM * CERT_MAX_PART; }
+
+// traj (d, n (d + 1)) and Xr (n (d + 1), d) from X (n (d + 1), r), the
+// basis U (r, d), the offset t0 (d) and the last-column flip
+void dpo_round_poses(const double* X, const double* U, const double* t0,
+                     int flip, double* traj, double* Xr, int n, int d, int r,
+                     void* stream) {
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_round_poses<Dc, Rc>), dim3(blocks_for(n, 256)),
+                           dim3(256), 0, (hipStream_t)stream, X, U, t0, flip,
+                           traj, Xr, n);
+      }))
+    dpo_bad_shape(d, r);
+}
+
+// count[0] = #{i : det(U^T Y_i) < 0}. ipart: CERT_MAX_PART scratch ints.
+void dpo_round_reflections(const double* X, const double* U, int* count,
+                           int* ipart, int n, int d, int r, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int g = cert_grid(n);
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((k_round_reflections<Dc, Rc>), dim3(g),
+                           dim3(CERT_BS), 0, s, X, U, ipart, n);
+      }))
+    dpo_bad_shape(d, r);
+  hipLaunchKernelGGL(k_round_count_finish, dim3(1), dim3(CERT_BS), 0, s,
+                     (const int*)ipart, g, count);
+}
+
+// in place on both layouts; anchor: (d + 1) x d block, not inside Xr
+void dpo_round_gauge(double* Xr, double* traj, const double* anchor, int n,
+                     int d, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const dim3 g(blocks_for(n, 256)), b(256);
+  if (d == 2)
+    hipLaunchKernelGGL(k_round_gauge<2>, g, b, 0, s, Xr, traj, anchor, n);
+  else if (d == 3)
+    hipLaunchKernelGGL(k_round_gauge<3>, g, b, 0, s, Xr, traj, anchor, n);
+  else
+    dpo_bad_shape(d, d);
+}
+
+}  // extern "C"

@@ -902,3 +902,94 @@ def refine_hd_stage(Q, ws, ctl: Tensor, d: int) -> None:
     """Hd = P_X(Q delta) with the per-block partials of <delta, Hd> in
     ws.part[:cert_partials(n)] (status RS_RUN only)."""
     _refine_stage(3, Q, ws, ctl, d, None)
+
+
+# ---------------------------------------------------------------------
+# Rounding to SE(d) (docs/DESIGN.md §19) — interface mirrors
+# cpu_ref.round_*. Nothing here synchronises with the host.
+# ---------------------------------------------------------------------
+_lib.dpo_round_gram.argtypes = [_c, _c, _c, _i, _i, _i, _c]
+_lib.dpo_round_gram_part.restype = _i
+_lib.dpo_round_poses.argtypes = [_c, _c, _c, _i, _c, _c, _i, _i, _i, _c]
+_lib.dpo_round_reflections.argtypes = [_c, _c, _c, _c, _i, _i, _i, _c]
+_lib.dpo_round_gauge.argtypes = [_c, _c, _c, _i, _i, _c]
+
+_ROUND_GRAM_PART = _lib.dpo_round_gram_part()
+
+
+def _round_dims(Xt: Tensor, d: int):
+    _chk(Xt)
+    assert Xt.dim() == 2 and Xt.shape[0] % (d + 1) == 0
+    N, r = Xt.shape
+    _check_shape(d, r)
+    return N // (d + 1), r
+
+
+def _round_basis(U: Tensor, like: Tensor, r: int, d: int) -> Tensor:
+    U = U.to(device=like.device, dtype=torch.float64).contiguous()
+    assert U.shape == (r, d)
+    return U
+
+
+def round_gram(Xt: Tensor, d: int) -> Tensor:
+    """S = sum_i Y_i Y_i^T (r, r) over the rotation rows of every pose
+    block, on Xt's device; bitwise run-to-run reproducible."""
+    n, r = _round_dims(Xt, d)
+    S = torch.empty(r, r, dtype=torch.float64, device=Xt.device)
+    part = torch.empty(_ROUND_GRAM_PART, dtype=torch.float64,
+                       device=Xt.device)
+    _lib.dpo_round_gram(_p(Xt), _p(S), _p(part), n, d, r, _stream(Xt))
+    return S
+
+
+def round_poses(Xt: Tensor, d: int, U: Tensor, t0: Tensor,
+                flip: bool = False):
+    """R_i = argmax_{SO(d)} tr(R^T U^T Y_i), t_i = U^T p_i - t0, with U's
+    last column negated under `flip`: the (d, n (d+1)) trajectory layout
+    and the Xt layout (n (d+1), d)."""
+    n, r = _round_dims(Xt, d)
+    U = _round_basis(U, Xt, r, d)
+    t0 = t0.to(device=Xt.device, dtype=torch.float64).contiguous()
+    assert t0.shape == (d,)
+    traj = torch.empty(d, n * (d + 1), dtype=torch.float64, device=Xt.device)
+    Xr = torch.empty(n * (d + 1), d, dtype=torch.float64, device=Xt.device)
+    _lib.dpo_round_poses(_p(Xt), _p(U), _p(t0), int(bool(flip)), _p(traj),
+                         _p(Xr), n, d, r, _stream(Xt))
+    return traj, Xr
+
+
+def round_reflections(Xt: Tensor, d: int, U: Tensor) -> Tensor:
+    """1-element int32 device tensor: poses with det(U^T Y_i) < 0."""
+    n, r = _round_dims(Xt, d)
+    U = _round_basis(U, Xt, r, d)
+    count = torch.empty(1, dtype=torch.int32, device=Xt.device)
+    ipart = torch.empty(_CERT_PART, dtype=torch.int32, device=Xt.device)
+    _lib.dpo_round_reflections(_p(Xt), _p(U), _p(count), _p(ipart), n, d, r,
+                               _stream(Xt))
+    return count
+
+
+def round_gauge(Xr: Tensor, traj: Tensor, d: int, anchor_pose: int) -> None:
+    """In place on both layouts: R_i <- R_a^T R_i, t_i <- R_a^T (t_i -
+    t_a) for a = anchor_pose, which is copied device to device first."""
+    _chk(Xr); _chk(traj)
+    dh = d + 1
+    n = Xr.shape[0] // dh
+    _check_shape(d, d)
+    assert Xr.shape == (n * dh, d) and traj.shape == (d, n * dh)
+    assert 0 <= anchor_pose < n
+    anchor = Xr[anchor_pose * dh:(anchor_pose + 1) * dh].clone()
+    _lib.dpo_round_gauge(_p(Xr), _p(traj), _p(anchor), n, d, _stream(Xr))
+
+
+def round_cost(Q, X: Tensor, G: Optional[Tensor] = None) -> Tensor:
+    """1-element device tensor f(X) = 0.5 <Q X, X> + <X, G> from the
+    BSR SpMM and dot kernels."""
+    _chk(X); _chk_q(Q, X)
+    assert X.shape[0] == Q.N
+    QX = bsr_spmm(Q.row_ptr, Q.col_idx, Q.vals, Q.n, Q.dh, X)
+    acc = torch.zeros(CTRL_SIZE, dtype=torch.float64, device=X.device)
+    dots(QX, X, None, acc, C_DOT0)
+    if G is not None:
+        dots(X, G.contiguous(), None, acc, C_DOT1)
+    return (0.5 * acc[C_DOT0] + acc[C_DOT1]).reshape(1)

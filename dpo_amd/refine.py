@@ -34,6 +34,7 @@ from .ops.cpu_ref import (CERT_SHAPES, REFINE_TCG_NAMES, RF_FX, RF_GN2,
                           refine_control)
 from .quadratic import (BSRMatrix, QuadraticProblem,
                         assemble_connection_laplacian)
+from .rounding import RoundingResult
 
 Tensor = torch.Tensor
 
@@ -208,6 +209,8 @@ class StaircaseResult:
     rank: int
     certificate: CertificateResult
     levels: List[StaircaseLevel] = field(default_factory=list)
+    # certified_solve(round=True): the SE(d) rounding of Xt
+    rounding: Optional["RoundingResult"] = None
 
     @property
     def status(self) -> CertificateStatus:
@@ -215,12 +218,15 @@ class StaircaseResult:
 
     def as_dict(self) -> dict:
         """The last level's refine and certificate fields, the level
-        records, `staircase_levels` and `final_rank`."""
+        records, `staircase_levels` and `final_rank`; with a rounding,
+        its `RoundingResult.as_dict()` fields as well."""
         out = self.levels[-1].refine.as_dict()
         out.update(self.certificate.as_dict())
         out["staircase_levels"] = len(self.levels)
         out["final_rank"] = self.rank
         out["levels"] = [lv.as_dict() for lv in self.levels]
+        if self.rounding is not None:
+            out.update(self.rounding.as_dict())
         return out
 
 
@@ -228,13 +234,18 @@ def certified_solve(measurements, n: int, d: int, Xt: Tensor, *,
                     weights: Optional[Sequence[float]] = None,
                     max_rank: Optional[int] = None,
                     refine_kw: Optional[dict] = None,
-                    certify_kw: Optional[dict] = None) -> StaircaseResult:
+                    certify_kw: Optional[dict] = None,
+                    round: bool = False) -> StaircaseResult:
     """Riemannian staircase from the lifted iterate Xt (N, r): refine to
     criticality, certify, and on NOT_OPTIMAL escape to rank r + 1 and
     repeat. Stops on any other verdict, or with NOT_OPTIMAL when r + 1 is
     outside the compiled shapes or above `max_rank`. Q is assembled once;
     `refine_kw` / `certify_kw` go to `refine_to_critical` /
-    `certify_solution`."""
+    `certify_solution`. With `round=True` the final level's iterate is
+    rounded to SE(d) on its device (`rounding.round_solution`,
+    mode="svd") and the result carries it as `rounding`: the trajectory,
+    its cost and the suboptimality gap, which bounds the distance to the
+    global optimum when the verdict is CERTIFIED."""
     assert Xt.dim() == 2 and Xt.shape[0] == n * (d + 1)
     cert_check_shape(d, Xt.shape[1])
     top = max(CERT_SHAPES[d])
@@ -256,5 +267,9 @@ def certified_solve(measurements, n: int, d: int, Xt: Tensor, *,
         levels.append(StaircaseLevel(r, ref, cert))
         if (cert.status != CertificateStatus.NOT_OPTIMAL
                 or r + 1 > max_rank):
-            return StaircaseResult(ref.Xt, r, cert, levels)
+            rounding = None
+            if round:
+                from .rounding import round_solution
+                rounding = round_solution(Q, ref.Xt, d, mode="svd")
+            return StaircaseResult(ref.Xt, r, cert, levels, rounding)
         X = escape_direction(Q, ref.Xt, cert.direction)

@@ -16,7 +16,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--robots", type=int, default=5)
@@ -47,7 +47,41 @@ def main():
                     help="certified solve: refine the gathered iterate to "
                          "criticality on the device, certify, and climb the "
                          "rank staircase on a not-optimal verdict")
-    args = ap.parse_args()
+    ap.add_argument("--round", action="store_true",
+                    help="round the lifted iterate to SE(d) on the device "
+                         "and add the rounded cost, the relaxation cost and "
+                         "the suboptimality gap to the JSON line (with "
+                         "--refine: of the certified solve's final level)")
+    return ap
+
+
+def rounding_fields(args, rounding, seconds=None):
+    """JSON fields of a `RoundingResult` under --round; nothing without
+    the flag, so the default output line is unchanged."""
+    if not args.round or rounding is None:
+        return {}
+    out = rounding.as_dict()
+    if seconds is not None:
+        out["round_s"] = seconds
+    return out
+
+
+def round_gathered(args, meas, n, d, Xt):
+    """--round without --refine: round the iterate as it stands."""
+    import torch
+    from dpo_amd.quadratic import assemble_connection_laplacian
+    from dpo_amd.rounding import round_solution
+    dev = torch.device(args.device)
+    Q = assemble_connection_laplacian(meas, n, d)
+    if dev.type != "cpu":
+        Q = Q.to(dev)
+    t0 = time.perf_counter()
+    res = round_solution(Q, Xt.detach().to(dev), d, mode="svd")
+    return rounding_fields(args, res, time.perf_counter() - t0)
+
+
+def main():
+    args = build_parser().parse_args()
 
     from dpo_amd.io_g2o import load_dataset
     from dpo_amd.comm import init_from_env
@@ -105,7 +139,8 @@ def main():
             t_cert = time.perf_counter()
             stair = certified_solve(
                 meas, n, meas[0].d,
-                Xt.detach().to(torch.device(args.device)), certify_kw=kw)
+                Xt.detach().to(torch.device(args.device)), certify_kw=kw,
+                round=args.round)
             out.update(stair.as_dict())
             out["certified_solve_s"] = time.perf_counter() - t_cert
     elif args.certify:
@@ -125,6 +160,11 @@ def main():
                 Xt.detach().to(torch.device(args.device)), **kw)
             out.update(cert.as_dict())
             out["certificate_s"] = time.perf_counter() - t_cert
+    if args.round and not args.refine:
+        Xt = (drv.gather_lifted_iterate() if args.driver == "dist"
+              else drv._gather_global_x().reshape(-1, args.r))
+        if Xt is not None and rank == 0:
+            out.update(round_gathered(args, meas, n, meas[0].d, Xt))
     if rank == 0:
         print(json.dumps(out))
 

@@ -14,7 +14,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--side", type=int, default=100)  # side^3 poses
     ap.add_argument("--agents", type=int, default=8)
@@ -30,7 +30,38 @@ def main():
                          "truth (a prior map); odometry = dead reckoning "
                          "(drifts over a 1M-pose chain)")
     ap.add_argument("--init-noise", type=float, default=0.05)
-    args = ap.parse_args()
+    ap.add_argument("--round", action="store_true",
+                    help="after the run, round the iterate to SE(3) on the "
+                         "device: adds round_ms and rounded_cost")
+    return ap
+
+
+def rounding_fields(args, drv, ma=None, n=0):
+    """--round: round every agent's iterate on the device against the
+    global anchor (round_ms, gather included) and evaluate f = 0.5 <Q X,
+    X> of the rounded trajectory on the device, Q with the measurements'
+    stored weights. Nothing without the flag."""
+    if not args.round or drv is None:
+        return {}
+    import numpy as np
+    import torch
+    from dpo_amd import ops
+    from dpo_amd.quadratic import assemble_connection_laplacian
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    T = drv.gather_final_trajectory(device=True)
+    torch.cuda.synchronize()
+    out = {"round_ms": (time.perf_counter() - t0) * 1e3}
+    if T is not None:
+        dev = torch.device(args.device)
+        Xr = torch.from_numpy(np.ascontiguousarray(T.T)).to(dev)
+        Q = assemble_connection_laplacian(ma, n, 3).to(dev)
+        out["rounded_cost"] = float(ops.backend_for(Xr).round_cost(Q, Xr))
+    return out
+
+
+def main():
+    args = build_parser().parse_args()
 
     import torch
     if args.device.startswith("cuda") and not torch.cuda.is_available():
@@ -115,6 +146,7 @@ def main():
         "gen_s": t_gen, "setup_s": t_setup, "run_s": t_run,
         "ms_per_round": t_run / max(res.iterations, 1) * 1e3,
     }
+    out.update(rounding_fields(args, drv, ma, n))
     if int(os.environ.get("RANK", "0")) == 0:
         print(json.dumps(out))
 

@@ -15,7 +15,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dataset", required=True)
     ap.add_argument("--device", default="cpu")
@@ -33,7 +33,41 @@ def main():
                     help="certified solve: refine the result to criticality "
                          "on the device, certify, and climb the rank "
                          "staircase on a not-optimal verdict")
-    args = ap.parse_args()
+    ap.add_argument("--round", action="store_true",
+                    help="round the lifted iterate to SE(d) on the device "
+                         "and add the rounded cost, the relaxation cost and "
+                         "the suboptimality gap to the JSON line (with "
+                         "--refine: of the certified solve's final level)")
+    return ap
+
+
+def rounding_fields(args, rounding, seconds=None):
+    """JSON fields of a `RoundingResult` under --round; nothing without
+    the flag, so the default output line is unchanged."""
+    if not args.round or rounding is None:
+        return {}
+    out = rounding.as_dict()
+    if seconds is not None:
+        out["round_s"] = seconds
+    return out
+
+
+def round_gathered(args, meas, n, d, Xt):
+    """--round without --refine: round the iterate as it stands."""
+    import torch
+    from dpo_amd.quadratic import assemble_connection_laplacian
+    from dpo_amd.rounding import round_solution
+    dev = torch.device(args.device)
+    Q = assemble_connection_laplacian(meas, n, d)
+    if dev.type != "cpu":
+        Q = Q.to(dev)
+    t0 = time.perf_counter()
+    res = round_solution(Q, Xt.detach().to(dev), d, mode="svd")
+    return rounding_fields(args, res, time.perf_counter() - t0)
+
+
+def main():
+    args = build_parser().parse_args()
 
     from dpo_amd.agent import PGOAgent
     from dpo_amd.io_g2o import load_dataset
@@ -60,7 +94,7 @@ def main():
         "grad_norm_opt": res.grad_norm_opt,
         "wall_s": wall,
     }
-    if args.certify or args.refine:
+    if args.certify or args.refine or args.round:
         import numpy as np
         import torch
         # r = d: the lifted iterate is the trajectory itself, transposed
@@ -74,13 +108,16 @@ def main():
         if args.refine:
             from dpo_amd.refine import certified_solve
             t_cert = time.perf_counter()
-            stair = certified_solve(meas, n, d, Xt, certify_kw=kw)
+            stair = certified_solve(meas, n, d, Xt, certify_kw=kw,
+                                    round=args.round)
             out.update(stair.as_dict())
             out["certified_solve_s"] = time.perf_counter() - t_cert
-        else:
+        elif args.certify:
             from dpo_amd.certify import certify_solution
             cert = certify_solution(meas, n, d, Xt, **kw)
             out.update(cert.as_dict())
+        if args.round and not args.refine:
+            out.update(round_gathered(args, meas, n, d, Xt))
     print(json.dumps(out))
     if args.dump_trajectory:
         from dpo_amd.logger import PGOLogger
