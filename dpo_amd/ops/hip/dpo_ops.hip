@@ -123,14 +123,16 @@ __device__ __forceinline__ void ctrl_store(double* p, double v) {
 // Returns true for exactly one block — the last to arrive — after every
 // block's prior vector-memory ops (incl. the dot atomics) have retired.
 // Split-K fan-in (guide G16): per-block vmcnt drain, then a device-scope
-// ticket; the winner resets the ticket for the next fused kernel.
-__device__ __forceinline__ bool fanin_last_block(double* ctrl) {
+// ticket; the winner resets the ticket for the next fused kernel. nblk is
+// the number of blocks that arrive: the grid's x extent in a single-agent
+// launch, the agent's own block count in a batched one.
+__device__ __forceinline__ bool fanin_last_block(double* ctrl, int nblk) {
   __syncthreads();
   __shared__ int is_last;
   if (threadIdx.x == 0) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     double old = atomicAdd(ctrl + C_TICKET, 1.0);
-    is_last = ((int)old == (int)gridDim.x - 1) ? 1 : 0;
+    is_last = ((int)old == nblk - 1) ? 1 : 0;
     if (is_last) ctrl_store(ctrl + C_TICKET, 0.0);
   }
   __syncthreads();
@@ -427,7 +429,7 @@ __device__ __forceinline__ void block_reduce_atomic(double v, double* dst) {
 // the last block run the control tail. A kernel that staged data through
 // LDS must have put a barrier behind its last LDS read before calling.
 template <int CF>
-__device__ __forceinline__ void finish_reduction(double* ctrl,
+__device__ __forceinline__ void finish_reduction(double* ctrl, int nblk,
                                                  int slot0, double d0,
                                                  int slot1 = -1,
                                                  double d1 = 0.0,
@@ -439,7 +441,7 @@ __device__ __forceinline__ void finish_reduction(double* ctrl,
   if (slot1 >= 0) block_reduce_atomic(d1, ctrl + slot1);
   if (slot2 >= 0) block_reduce_atomic(d2, ctrl + slot2);
   if (CF != CF_NONE) {
-    const bool last = fanin_last_block(ctrl);
+    const bool last = fanin_last_block(ctrl, nblk);
     if (last && threadIdx.x == 0) run_ctrl_tail(CF, ctrl, ta);
     if (CF == CF_ACCEPT_OUT && last) ctrl_publish(ctrl, ta);
   }
@@ -612,15 +614,17 @@ __global__ void k_bsr_spmm_gen(const int* __restrict__ row_ptr,
 #define DPO_MAX_R 8
 #define DPO_MAX_DH 4
 
-template <int D, int R, int CF = CF_NONE>
-__global__ void k_proj_dots(const double* __restrict__ X,
-                            const double* __restrict__ V,
-                            const double* __restrict__ G,
-                            double* __restrict__ out,
-                            const double* __restrict__ dotWith,
-                            double* __restrict__ ctrl,
-                            int n, int dot_slot, int dot_slot2,
-                            int guard) {
+// The kernels of the dense solve chain and of the evaluation keep their
+// bodies in __device__ functions (*_body): the single-agent __global__
+// kernel calls the body with its own grid extents, the batched wrapper
+// (kb_*, further down) with those of the agent it serves. nblk is the
+// number of blocks that take part in the kernel's fan-in.
+template <int D, int R, int CF>
+__device__ __forceinline__ void proj_dots_body(
+    const double* __restrict__ X, const double* __restrict__ V,
+    const double* __restrict__ G, double* __restrict__ out,
+    const double* __restrict__ dotWith, double* __restrict__ ctrl, int n,
+    int dot_slot, int dot_slot2, int guard, int nblk) {
   if (guarded_off(ctrl, guard)) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   constexpr int dh = D + 1;
@@ -657,7 +661,20 @@ __global__ void k_proj_dots(const double* __restrict__ X,
         }
       }
   }
-  finish_reduction<CF>(ctrl, dot_slot, dot_pw, dot_slot2, dot_vx);
+  finish_reduction<CF>(ctrl, nblk, dot_slot, dot_pw, dot_slot2, dot_vx);
+}
+
+template <int D, int R, int CF = CF_NONE>
+__global__ void k_proj_dots(const double* __restrict__ X,
+                            const double* __restrict__ V,
+                            const double* __restrict__ G,
+                            double* __restrict__ out,
+                            const double* __restrict__ dotWith,
+                            double* __restrict__ ctrl,
+                            int n, int dot_slot, int dot_slot2,
+                            int guard) {
+  proj_dots_body<D, R, CF>(X, V, G, out, dotWith, ctrl, n, dot_slot,
+                           dot_slot2, guard, (int)gridDim.x);
 }
 
 // Fused block-Jacobi preconditioner apply + tangent projection (+ dot
@@ -745,7 +762,7 @@ __global__ void k_precond_proj(const double* __restrict__ L,
           dot = fma(Vt[c][k], Ri[c * R + k], dot);
       }
   }
-  finish_reduction<CF>(ctrl, dot_slot, dot);
+  finish_reduction<CF>(ctrl, gridDim.x, dot_slot, dot);
 }
 
 // Wide (element-per-thread) tangent projection for LARGE agents: same
@@ -795,7 +812,7 @@ __global__ void k_proj_wide(const double* __restrict__ X,
     }
   }
   __syncthreads();
-  finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1);
+  finish_reduction<CF>(ctrl, gridDim.x, dot_slot, d0, dot_slot2, d1);
 }
 
 // ---------------------------------------------------------------------
@@ -821,20 +838,15 @@ __global__ void k_proj_wide(const double* __restrict__ X,
 // writes its own pose's tile into buffer C_ITER & 1 and reads the other,
 // so no block reads what another writes, and the choice travels with the
 // control block across the continuation graph.
-template <int D, int R, int MODE, int CF = CF_NONE, int AUX = 0>
-__global__ void k_hess_fused(const int* __restrict__ row_ptr,
-                             const int* __restrict__ col_idx,
-                             const double* __restrict__ vals,
-                             const double* __restrict__ V,
-                             const double* __restrict__ X,
-                             const double* __restrict__ G,
-                             double* __restrict__ out,
-                             const double* __restrict__ dotW,
-                             double* __restrict__ ctrl,
-                             int n, int dot_slot, int dot_slot2,
-                             int dot_slot3, int guard,
-                             double* __restrict__ out2,
-                             double* __restrict__ zero_out, TailArgs ta) {
+template <int D, int R, int MODE, int CF, int AUX>
+__device__ __forceinline__ void hess_fused_body(
+    const int* __restrict__ row_ptr, const int* __restrict__ col_idx,
+    const double* __restrict__ vals, const double* __restrict__ V,
+    const double* __restrict__ X, const double* __restrict__ G,
+    double* __restrict__ out, const double* __restrict__ dotW,
+    double* __restrict__ ctrl, int n, int dot_slot, int dot_slot2,
+    int dot_slot3, int guard, double* __restrict__ out2,
+    double* __restrict__ zero_out, TailArgs ta, int nblk) {
   if (guarded_off(ctrl, guard)) {
     // the CF_ACCEPT_OUT publish step is unguarded, like the two launches
     // it replaces: the host reads the control block whatever the status
@@ -968,8 +980,28 @@ __global__ void k_hess_fused(const int* __restrict__ row_ptr,
       }
     }
   }
-  finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1,
+  finish_reduction<CF>(ctrl, nblk, dot_slot, d0, dot_slot2, d1,
                        MODE == 0 ? dot_slot3 : -1, d2, ta);
+}
+
+template <int D, int R, int MODE, int CF = CF_NONE, int AUX = 0>
+__global__ void k_hess_fused(const int* __restrict__ row_ptr,
+                             const int* __restrict__ col_idx,
+                             const double* __restrict__ vals,
+                             const double* __restrict__ V,
+                             const double* __restrict__ X,
+                             const double* __restrict__ G,
+                             double* __restrict__ out,
+                             const double* __restrict__ dotW,
+                             double* __restrict__ ctrl,
+                             int n, int dot_slot, int dot_slot2,
+                             int dot_slot3, int guard,
+                             double* __restrict__ out2,
+                             double* __restrict__ zero_out, TailArgs ta) {
+  hess_fused_body<D, R, MODE, CF, AUX>(row_ptr, col_idx, vals, V, X, G, out,
+                                       dotW, ctrl, n, dot_slot, dot_slot2,
+                                       dot_slot3, guard, out2, zero_out, ta,
+                                       (int)gridDim.x);
 }
 
 // ---------------------------------------------------------------------
@@ -1057,7 +1089,7 @@ __global__ void k_hess_wide(const int* __restrict__ row_ptr,
     }
     __syncthreads();  // sAcc/sX reuse barrier for CF tail safety
   }
-  finish_reduction<CF>(ctrl, dot_slot, d0, dot_slot2, d1,
+  finish_reduction<CF>(ctrl, gridDim.x, dot_slot, d0, dot_slot2, d1,
                        MODE == 0 ? dot_slot3 : -1, d2, ta);
 }
 
@@ -1265,15 +1297,15 @@ __global__ void k_polar_affine(const double* __restrict__ A,
 // The j loop is SPLIT across gridDim.y so small problems still fill the
 // chip (MI355X: 256 CUs want >> 256 workgroups); partial sums combine
 // with fp64 atomics into the zeroed output.
+// jsplit is the number of j chunks (the grid's y extent in a single-agent
+// launch, the agent's own split in a batched one).
 template <int R>
-__global__ void k_precond_dense(const float* __restrict__ Minv,
-                                const double* __restrict__ V,
-                                double* __restrict__ Z,
-                                int N, const double* __restrict__ ctrl,
-                                int guard) {
+__device__ __forceinline__ void precond_dense_body(
+    const float* __restrict__ Minv, const double* __restrict__ V,
+    double* __restrict__ Z, int N, const double* __restrict__ ctrl,
+    int guard, int jsplit) {
   if (guarded_off(ctrl, guard)) return;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int jsplit = gridDim.y;
   const int jchunk = (N + jsplit - 1) / jsplit;
   const int j_lo = blockIdx.y * jchunk;
   const int j_hi = min(N, j_lo + jchunk);
@@ -1326,6 +1358,15 @@ __global__ void k_precond_dense(const float* __restrict__ Minv,
   }
 }
 
+template <int R>
+__global__ void k_precond_dense(const float* __restrict__ Minv,
+                                const double* __restrict__ V,
+                                double* __restrict__ Z,
+                                int N, const double* __restrict__ ctrl,
+                                int guard) {
+  precond_dense_body<R>(Minv, V, Z, N, ctrl, guard, (int)gridDim.y);
+}
+
 // Block-Jacobi apply: per pose solve (L L^T) z = v with stored Cholesky
 // factors L (n, dh, dh). One thread per pose per rhs column.
 template <int DH>
@@ -1354,17 +1395,13 @@ __global__ void k_precond_jacobi(const double* __restrict__ L,
 // Two elements per thread: the kernel is a pure fp64 stream (4 reads
 // + 4 writes per element) and was memory-latency-bound at 1M-pose
 // scale with one 8-byte access per lane per array.
-template <int CF = CF_NONE>
-__global__ void k_tcg_update(double* __restrict__ eta,
-                             double* __restrict__ rvec,
-                             const double* __restrict__ delta0,
-                             const double* __restrict__ Hd,
-                             double* __restrict__ eta_snap,
-                             double* __restrict__ delta_snap,
-                             double* __restrict__ ctrl,
-                             long total,
-                             double* __restrict__ zero_out,
-                             const double* __restrict__ delta1) {
+template <int CF>
+__device__ __forceinline__ void tcg_update_body(
+    double* __restrict__ eta, double* __restrict__ rvec,
+    const double* __restrict__ delta0, const double* __restrict__ Hd,
+    double* __restrict__ eta_snap, double* __restrict__ delta_snap,
+    double* __restrict__ ctrl, long total, double* __restrict__ zero_out,
+    const double* __restrict__ delta1, int nblk) {
   if (guarded_off(ctrl, ST_RUN)) return;
   const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
   const double coef = ctrl[C_COEF];
@@ -1399,7 +1436,22 @@ __global__ void k_tcg_update(double* __restrict__ eta,
       }
     }
   }
-  finish_reduction<CF>(ctrl, stop_pending ? -1 : C_DOT1, rr);
+  finish_reduction<CF>(ctrl, nblk, stop_pending ? -1 : C_DOT1, rr);
+}
+
+template <int CF = CF_NONE>
+__global__ void k_tcg_update(double* __restrict__ eta,
+                             double* __restrict__ rvec,
+                             const double* __restrict__ delta0,
+                             const double* __restrict__ Hd,
+                             double* __restrict__ eta_snap,
+                             double* __restrict__ delta_snap,
+                             double* __restrict__ ctrl,
+                             long total,
+                             double* __restrict__ zero_out,
+                             const double* __restrict__ delta1) {
+  tcg_update_body<CF>(eta, rvec, delta0, Hd, eta_snap, delta_snap, ctrl,
+                      total, zero_out, delta1, (int)gridDim.x);
 }
 
 // delta = -z + beta * delta
@@ -1441,13 +1493,11 @@ __global__ void k_form_step(double* __restrict__ step,
 // single fma per element as k_form_step), stores it, and retracts
 // X + step into Xprop.
 template <int D, int R>
-__global__ void k_candidate(double* __restrict__ ctrl,
-                            double* __restrict__ step,
-                            const double* __restrict__ eta,
-                            const double* __restrict__ eta_snap,
-                            const double* __restrict__ delta_snap,
-                            const double* __restrict__ X,
-                            double* __restrict__ Xprop, int n) {
+__device__ __forceinline__ void candidate_body(
+    double* __restrict__ ctrl, double* __restrict__ step,
+    const double* __restrict__ eta, const double* __restrict__ eta_snap,
+    const double* __restrict__ delta_snap, const double* __restrict__ X,
+    double* __restrict__ Xprop, int n) {
   if (guarded_off(ctrl, ST_TCG_STOP)) return;
   __shared__ CandSel sel_sh;
   if (threadIdx.x == 0) {
@@ -1478,6 +1528,17 @@ __global__ void k_candidate(double* __restrict__ ctrl,
       Mt[c][k] = fma(1.0, st, X[base + c * R + k]);
     }
   polar_tile<D, R>(Mt, Xprop + base);
+}
+
+template <int D, int R>
+__global__ void k_candidate(double* __restrict__ ctrl,
+                            double* __restrict__ step,
+                            const double* __restrict__ eta,
+                            const double* __restrict__ eta_snap,
+                            const double* __restrict__ delta_snap,
+                            const double* __restrict__ X,
+                            double* __restrict__ Xprop, int n) {
+  candidate_body<D, R>(ctrl, step, eta, eta_snap, delta_snap, X, Xprop, n);
 }
 
 // out = a*A + b*B elementwise (unguarded helper)
@@ -1532,7 +1593,7 @@ static void launch_ctrl_tail(double* ctrl, hipStream_t s) {
 }
 
 // end of the unrolled loop: cap at max_inner
-__global__ void k_ctrl_tcg_end(double* ctrl) {
+__device__ __forceinline__ void ctrl_tcg_end_body(double* ctrl) {
   if (threadIdx.x != 0) return;
   if (ctrl[C_STATUS] != (double)ST_RUN) return;
   ctrl[C_STATUS] = (double)ST_TCG_STOP;
@@ -1540,6 +1601,7 @@ __global__ void k_ctrl_tcg_end(double* ctrl) {
   ctrl[C_HLEN] = ctrl[C_ITER];
   ctrl[C_USE_CURRENT] = 1.0;
 }
+__global__ void k_ctrl_tcg_end(double* ctrl) { ctrl_tcg_end_body(ctrl); }
 
 // candidate selection for the current radius: replay the stored Krylov
 // scalars, find the truncation point and the model decrease.
@@ -1580,13 +1642,11 @@ __global__ void k_q_assemble(double* __restrict__ vals,
 
 // G values: Gt[local_pose[e]] += -w[e] * E0[e] @ nbr[slot[e]]
 // one thread per (edge, c, k) output element
-__global__ void k_g_assemble(double* __restrict__ Gt,
-                             const double* __restrict__ E0,
-                             const long* __restrict__ local_pose,
-                             const long* __restrict__ nbr_slot,
-                             const double* __restrict__ nbr,
-                             const double* __restrict__ w,
-                             int ne, int dh, int r) {
+__device__ __forceinline__ void g_assemble_body(
+    double* __restrict__ Gt, const double* __restrict__ E0,
+    const long* __restrict__ local_pose, const long* __restrict__ nbr_slot,
+    const double* __restrict__ nbr, const double* __restrict__ w, int ne,
+    int dh, int r) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)ne * dh * r) return;
   const int e = i / (dh * r);
@@ -1597,6 +1657,16 @@ __global__ void k_g_assemble(double* __restrict__ Gt,
   double acc = 0.0;
   for (int b = 0; b < dh; ++b) acc = fma(Ee[c * dh + b], Xn[b * r + k], acc);
   atomicAdd(&Gt[((size_t)local_pose[e] * dh + c) * r + k], -w[e] * acc);
+}
+
+__global__ void k_g_assemble(double* __restrict__ Gt,
+                             const double* __restrict__ E0,
+                             const long* __restrict__ local_pose,
+                             const long* __restrict__ nbr_slot,
+                             const double* __restrict__ nbr,
+                             const double* __restrict__ w,
+                             int ne, int dh, int r) {
+  g_assemble_body(Gt, E0, local_pose, nbr_slot, nbr, w, ne, dh, r);
 }
 
 // ---------------------------------------------------------------------
@@ -1811,15 +1881,20 @@ static void launch_hess_fused(const int* rp, const int* ci,
 // compute<->SDMA dependencies in replayed graphs are part of the same
 // ROCm 7.2 ordering fragility the launch fences work around, so the
 // captured bodies use plain kernels only.
-__global__ void k_dzero(double* p, long n) {
+__device__ __forceinline__ void dzero_body(double* p, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0.0;
 }
+__global__ void k_dzero(double* p, long n) { dzero_body(p, n); }
 // two buffers in one launch (the solve head's G_buf and control block)
-__global__ void k_dzero2(double* p, long n, double* q, long m) {
+__device__ __forceinline__ void dzero2_body(double* p, long n, double* q,
+                                            long m) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = 0.0;
   if (i < m) q[i] = 0.0;
+}
+__global__ void k_dzero2(double* p, long n, double* q, long m) {
+  dzero2_body(p, n, q, m);
 }
 __global__ void k_ctrl_to_host(const double* __restrict__ src,
                                double* __restrict__ dst, int n) {
@@ -2181,6 +2256,15 @@ struct DpoCtx {
   // fixed 3-double eval destination for the group fan-out path (a
   // stable pointer keeps the eval graph cache hot)
   double* eval3 = nullptr;
+  // Advanced whenever a pointer that a batch descriptor copies out of this
+  // context changes (problem / G-structure setters); a DpoGroup compares
+  // it before each batched launch and rebuilds its descriptors and graphs
+  // when it moved. Re-binding the same buffers (a Q rebuild or a GNC
+  // re-weighting in place) leaves it alone. The linear term does not
+  // count: set_problem resets Gt and the round assembly sets it again,
+  // which invalidates the per-agent graphs (they hold Gt as an argument)
+  // but not a descriptor, which always names G_buf.
+  long desc_stamp = 0;
   void invalidate_graphs() {
     solve_graph.reset();
     cont_graph.reset();
@@ -2236,12 +2320,21 @@ static inline void fence_wait(DpoCtx* c, int which, hipStream_t s) {
                      c->fences + which);
 }
 
+// The linear term a round assembly leaves bound: G_buf when the agent has
+// shared edges, none otherwise. ctx_assemble_g sets it when it enqueues
+// the assembly; the batched path, whose kernels take it from the
+// descriptor, sets it through the same function (the per-agent shrink
+// loop of solve_postsync reads c->Gt).
+static inline const double* ctx_bind_round_g(DpoCtx* c) {
+  c->Gt = c->g_ne > 0 ? c->G_buf : nullptr;
+  return c->Gt;
+}
+
 // with_ctrl: the launch that clears G_buf clears the control block too
 // (solve head).
 static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s,
                            bool with_ctrl = false) {
-  if (c->g_ne == 0) {
-    c->Gt = nullptr;
+  if (!ctx_bind_round_g(c)) {
     if (with_ctrl) dzero(c->ctrl, CTRL_SIZE, s);
     return;
   }
@@ -2256,7 +2349,6 @@ static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s,
                      dim3(((long)c->g_ne * c->dh * c->r + 255) / 256),
                      dim3(256), 0, s, c->G_buf, c->g_E0, c->g_local_pose,
                      c->g_nbr_slot, nbr, c->g_w, c->g_ne, c->dh, c->r);
-  c->Gt = c->G_buf;
 }
 
 // The buffer the solve body must have cleared before each dense apply:
@@ -2364,6 +2456,9 @@ void dpo_ctx_set_problem(void* h, const int* rp, const int* ci,
   if (c->q_vals != vals || c->Minv != Minv || c->Ljac != Ljac
       || c->Gt != Gt || c->q_rp != rp)
     c->invalidate_graphs();
+  if (c->q_vals != vals || c->Minv != Minv || c->Ljac != Ljac
+      || c->q_rp != rp || c->q_ci != ci)
+    c->desc_stamp++;
   c->q_rp = rp; c->q_ci = ci; c->q_vals = vals;
   c->Gt = Gt; c->Minv = Minv; c->Ljac = Ljac;
 }
@@ -2642,6 +2737,11 @@ static void enqueue_solve_cont(DpoCtx* c, double* X, double accept_rho,
   enqueue_solve_tail(c, X, accept_rho, s);
 }
 
+static inline const void* solve_key_scalars(double tol, double accept_rho) {
+  return (const void*)((intptr_t)(tol * 1e9)
+                       ^ ((intptr_t)(accept_rho * 1e6) << 36));
+}
+
 // Ensure the solve graph for (X, nbr, tol, Delta0) is cached; run the
 // pre-sync sequence (via graph replay or eagerly) on stream s WITHOUT
 // the final synchronize. Returns true when the sequence was enqueued
@@ -2659,7 +2759,9 @@ static bool solve_presync(DpoCtx* c, double* X, const double* nbr,
     fence_wait(c, F_SOLVE_OUT, s);
     return true;
   }
-  const void* key[4] = {X, nbr, (const void*)(intptr_t)(tol * 1e9),
+  // accept_rho is an argument of the captured acceptance test too: it
+  // shares a key slot with tol
+  const void* key[4] = {X, nbr, solve_key_scalars(tol, accept_rho),
                         (const void*)(intptr_t)Delta0};
   const int seg = solve_segment(c);
   const bool launched = graph_cache_launch(
@@ -2692,7 +2794,9 @@ static bool solve_continue(DpoCtx* c, double* X, const double* nbr,
   if (seg >= c->max_inner) return false;
   c->n_conts++;
   fence_signal(c, F_SOLVE_IN, s);
-  const void* key[4] = {X, nbr, (const void*)(intptr_t)(tol * 1e9),
+  // accept_rho is an argument of the captured acceptance test too: it
+  // shares a key slot with tol
+  const void* key[4] = {X, nbr, solve_key_scalars(tol, accept_rho),
                         (const void*)(intptr_t)Delta0};
   const bool launched = graph_cache_launch(
       c->cont_graph, key, c->cap_stream, s, [&](hipStream_t cs) {
@@ -2710,9 +2814,12 @@ static bool solve_continue(DpoCtx* c, double* X, const double* nbr,
 // attempt's kernels no-op via the ctrl guard once a candidate is
 // accepted) behind a single stream sync, instead of a host round-trip
 // per attempt.
+// commit == false leaves X <- Xprop of an accepted step to the caller
+// (the batched finish commits every member with one launch).
 static int solve_postsync(DpoCtx* c, double* X, double accept_rho,
                           int max_shrink, int compute_final_gn,
-                          double* stats_out, hipStream_t s) {
+                          double* stats_out, hipStream_t s,
+                          bool commit = true) {
   int st = (int)c->ctrl_host[C_STATUS];
   if (st == ST_TCG_STOP && max_shrink > 0) {
     for (int attempt = 1; attempt <= max_shrink; ++attempt) {
@@ -2726,8 +2833,9 @@ static int solve_postsync(DpoCtx* c, double* X, double accept_rho,
   const int shrinks = (int)c->ctrl_host[C_SHRINKS];
   int status = st;
   if (st == ST_ACCEPTED) {
-    DPO_CHECK(hipMemcpyAsync(X, c->Xprop, c->total * sizeof(double),
-                             hipMemcpyDeviceToDevice, s));
+    if (commit)
+      DPO_CHECK(hipMemcpyAsync(X, c->Xprop, c->total * sizeof(double),
+                               hipMemcpyDeviceToDevice, s));
   } else if (st == ST_TCG_STOP) {
     status = ST_GIVE_UP;  // every radius rejected: keep the iterate
   }
@@ -3003,6 +3111,9 @@ void dpo_ctx_set_gdata(void* h, const double* E0, const long* local_pose,
                        const long* nbr_slot, const double* w, int ne) {
   DpoCtx* c = (DpoCtx*)h;
   if (c->g_E0 != E0 || c->g_w != w) c->invalidate_graphs();
+  if (c->g_E0 != E0 || c->g_w != w || c->g_local_pose != local_pose
+      || c->g_nbr_slot != nbr_slot || c->g_ne != ne)
+    c->desc_stamp++;
   c->g_E0 = E0; c->g_local_pose = local_pose; c->g_nbr_slot = nbr_slot;
   c->g_w = w; c->g_ne = ne;
 }
@@ -3071,6 +3182,350 @@ void dpo_eval_join(void* h, void* join_stream) {
   DPO_CHECK(hipStreamWaitEvent((hipStream_t)join_stream, c->done_event, 0));
 }
 
+}  // extern "C"
+
+// --- batched agents: one launch per stage for a list of agents --------
+// The agents of one colour are independent problems of the same shape
+// (d, r), each of 2-6 workgroups per kernel. A batched wrapper (kb_*)
+// serves a whole list with one launch: the last grid dimension is the
+// agent, desc[agent] holds what the single-agent launch passes as
+// arguments, and the wrapper calls the same *_body. A block at or beyond
+// its own agent's extent returns at once, before any barrier, dot atomic
+// or ticket, so every agent's block decomposition — and with it its
+// arithmetic — is that of its single-agent launch. Guards are tested per
+// agent on its own control block.
+struct BatchDesc {
+  // problem (DpoCtx::q_*, Minv) and G-assembly structure (DpoCtx::g_*)
+  const int *q_rp, *q_ci;
+  const double* q_vals;
+  const float* Minv;
+  const double* g_E0;
+  const long *g_local_pose, *g_nbr_slot;
+  const double* g_w;
+  // iterate, packed neighbour buffer, linear term (nullptr: none)
+  double* X;
+  const double* nbr;
+  const double* Gt;
+  // work vectors and control block
+  double *G_buf, *grad, *eta, *delta, *delta1, *rvec, *z, *Hd, *step, *Xprop;
+  double *eta_snap, *delta_snap, *ctrl;
+  double* prezero_z;  // ctx_prezero_z
+  // TailArgs destinations and fences
+  double* ctrl_host_dev;
+  double* eval3;
+  unsigned int* fences;
+  long total, gtotal;  // gtotal: elements of G_buf to clear (0: no G term)
+  int n, N, g_ne;
+  // per-agent grid extents
+  int nb_pose, nb_upd, nb_dense, jsplit, nb_gasm, nb_zero, nb_zero2, nb_copy;
+};
+
+static void batch_desc_extents(BatchDesc& b, int dh, int r) {
+  b.nb_pose = blocks_for(b.n, 256);
+  b.nb_upd = blocks_for((b.total + 3) / 4, 256);
+  b.nb_dense = blocks_for(b.N, 256);
+  b.jsplit = precond_dense_jsplit(b.N);
+  b.nb_gasm = blocks_for((long)b.g_ne * dh * r, 256);
+  b.nb_zero = blocks_for(b.gtotal, 256);
+  b.nb_zero2 = blocks_for(b.gtotal > CTRL_SIZE ? b.gtotal : (long)CTRL_SIZE,
+                          256);
+  b.nb_copy = blocks_for(b.total, 256);
+}
+
+__global__ void kb_dzero(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_zero) return;
+  dzero_body(a.G_buf, a.gtotal);
+}
+
+__global__ void kb_dzero2(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_zero2) return;
+  dzero2_body(a.G_buf, a.gtotal, a.ctrl, (long)CTRL_SIZE);
+}
+
+__global__ void kb_g_assemble(const BatchDesc* __restrict__ desc, int dh,
+                              int r) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_gasm) return;
+  g_assemble_body(a.G_buf, a.g_E0, a.g_local_pose, a.g_nbr_slot, a.nbr,
+                  a.g_w, a.g_ne, dh, r);
+}
+
+// The four Hessian stages of the dense chain, with the operands the
+// per-agent sequence gives them (enqueue_solve_head, launch_hd_folded,
+// enqueue_candidate, eval_terms).
+enum BatchHess { BH_GRAD = 0, BH_HD = 1, BH_CAND = 2, BH_EVAL = 3 };
+
+template <int D, int R, int ROLE, int CF>
+__global__ void kb_hess(const BatchDesc* __restrict__ desc, TailArgs ta) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_pose) return;
+  const int s3 = a.Gt ? C_DOT2 : -1;
+  if (ROLE == BH_GRAD) {
+    hess_fused_body<D, R, 0, CF, 1>(a.q_rp, a.q_ci, a.q_vals, a.X, a.X, a.Gt,
+                                    a.grad, nullptr, a.ctrl, a.n, C_DOT1,
+                                    C_DOT0, s3, -1, a.rvec, a.prezero_z, ta,
+                                    a.nb_pose);
+  } else if (ROLE == BH_HD) {
+    hess_fused_body<D, R, 0, CF, 2>(a.q_rp, a.q_ci, a.q_vals, nullptr, a.X,
+                                    nullptr, a.Hd, a.z, a.ctrl, a.n, C_DOT0,
+                                    -1, -1, ST_RUN, a.delta1, a.delta, ta,
+                                    a.nb_pose);
+  } else if (ROLE == BH_CAND) {
+    ta.dst = a.ctrl_host_dev;
+    ta.fence = a.fences + F_SOLVE_OUT;
+    hess_fused_body<D, R, 1, CF, 0>(a.q_rp, a.q_ci, a.q_vals, a.Xprop,
+                                    nullptr, a.Gt, nullptr, nullptr, a.ctrl,
+                                    a.n, C_DOT0, C_DOT2, -1, ST_TCG_STOP,
+                                    nullptr, nullptr, ta, a.nb_pose);
+  } else {
+    ta.dst = a.eval3;
+    ta.fence = a.fences + F_EVAL_OUT;
+    hess_fused_body<D, R, 0, CF, 0>(a.q_rp, a.q_ci, a.q_vals, a.X, a.X, a.Gt,
+                                    a.grad, nullptr, a.ctrl, a.n, C_DOT1,
+                                    C_DOT0, s3, -1, nullptr, nullptr, ta,
+                                    a.nb_pose);
+  }
+}
+
+// z = Minv rvec; grid (max blocks, max j-split, agents)
+template <int R>
+__global__ void kb_precond_dense(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.z];
+  if ((int)blockIdx.x >= a.nb_dense || (int)blockIdx.y >= a.jsplit) return;
+  precond_dense_body<R>(a.Minv, a.rvec, a.z, a.N, a.ctrl, ST_RUN, a.jsplit);
+}
+
+// z = P_X(z), <z, rvec>, tail CF_Z0 / CF_BETA
+template <int D, int R, int CF>
+__global__ void kb_proj_dots(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_pose) return;
+  proj_dots_body<D, R, CF>(a.X, a.z, nullptr, a.z, a.rvec, a.ctrl, a.n,
+                           C_DOT0, -1, ST_RUN, a.nb_pose);
+}
+
+template <int CF>
+__global__ void kb_tcg_update(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_upd) return;
+  tcg_update_body<CF>(a.eta, a.rvec, a.delta, a.Hd, a.eta_snap, a.delta_snap,
+                      a.ctrl, a.total, a.prezero_z, a.delta1, a.nb_upd);
+}
+
+template <int D, int R>
+__global__ void kb_candidate(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_pose) return;
+  candidate_body<D, R>(a.ctrl, a.step, a.eta, a.eta_snap, a.delta_snap, a.X,
+                       a.Xprop, a.n);
+}
+
+__global__ void kb_ctrl_tcg_end(const BatchDesc* __restrict__ desc) {
+  ctrl_tcg_end_body(desc[blockIdx.y].ctrl);
+}
+
+// X <- Xprop for every agent whose bit is set in mask (the members that
+// ended ST_ACCEPTED); replaces one device-to-device copy per agent.
+__global__ void kb_commit(const BatchDesc* __restrict__ desc,
+                          unsigned int mask) {
+  if (!((mask >> blockIdx.y) & 1u)) return;
+  const BatchDesc& a = desc[blockIdx.y];
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < a.total) a.X[i] = a.Xprop[i];
+}
+
+// Wait on and consume n fences, one lane per fence; the bounded spin of
+// k_fence_wait.
+__global__ void k_fence_wait_many(unsigned int* const* __restrict__ f,
+                                  int n) {
+  const int i = threadIdx.x;
+  if (i < n) {
+    long spins = 0;
+    while (__hip_atomic_load(f[i], __ATOMIC_ACQUIRE,
+                             __HIP_MEMORY_SCOPE_AGENT) == 0u) {
+      __builtin_amdgcn_s_sleep(64);
+      if (++spins > 30000000L) __builtin_trap();
+    }
+    __hip_atomic_store(f[i], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// Grid extents of a batch: the maximum of every per-agent extent.
+struct BatchExtents {
+  int k = 0, pose = 1, upd = 1, dense = 1, js = 1, gasm = 0, zero = 0,
+      zero2 = 1, copy = 1;
+  void add(const BatchDesc& b) {
+    ++k;
+    pose = b.nb_pose > pose ? b.nb_pose : pose;
+    upd = b.nb_upd > upd ? b.nb_upd : upd;
+    dense = b.nb_dense > dense ? b.nb_dense : dense;
+    js = b.jsplit > js ? b.jsplit : js;
+    gasm = b.nb_gasm > gasm ? b.nb_gasm : gasm;
+    zero = b.nb_zero > zero ? b.nb_zero : zero;
+    zero2 = b.nb_zero2 > zero2 ? b.nb_zero2 : zero2;
+    copy = b.nb_copy > copy ? b.nb_copy : copy;
+  }
+};
+
+// Launchers. d / r select the instantiation; dd is the device array.
+template <int ROLE, int CF>
+static void launch_kb_hess(const BatchDesc* dd, const BatchExtents& e, int d,
+                           int r, const TailArgs& ta, hipStream_t s) {
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((kb_hess<Dc, Rc, ROLE, CF>), dim3(e.pose, e.k),
+                           dim3(256), 0, s, dd, ta);
+      }))
+    dpo_bad_shape(d, r);
+}
+
+static void launch_kb_precond(const BatchDesc* dd, const BatchExtents& e,
+                              int r, hipStream_t s) {
+  if (!dispatch_r(r, [&](auto Rc) {
+        hipLaunchKernelGGL((kb_precond_dense<Rc>), dim3(e.dense, e.js, e.k),
+                           dim3(256), 0, s, dd);
+      }))
+    dpo_bad_shape(-1, r);
+}
+
+template <int CF>
+static void launch_kb_proj(const BatchDesc* dd, const BatchExtents& e, int d,
+                           int r, hipStream_t s) {
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((kb_proj_dots<Dc, Rc, CF>), dim3(e.pose, e.k),
+                           dim3(256), 0, s, dd);
+      }))
+    dpo_bad_shape(d, r);
+}
+
+static void launch_kb_candidate(const BatchDesc* dd, const BatchExtents& e,
+                                int d, int r, hipStream_t s) {
+  if (!dispatch_dr(d, r, [&](auto Dc, auto Rc) {
+        hipLaunchKernelGGL((kb_candidate<Dc, Rc>), dim3(e.pose, e.k),
+                           dim3(256), 0, s, dd);
+      }))
+    dpo_bad_shape(d, r);
+}
+
+static void launch_kb_gzero_assemble(const BatchDesc* dd,
+                                     const BatchExtents& e, int d, int r,
+                                     bool with_ctrl, hipStream_t s) {
+  if (with_ctrl)
+    hipLaunchKernelGGL(kb_dzero2, dim3(e.zero2, e.k), dim3(256), 0, s, dd);
+  else if (e.zero > 0)
+    hipLaunchKernelGGL(kb_dzero, dim3(e.zero, e.k), dim3(256), 0, s, dd);
+  if (e.gasm > 0)
+    hipLaunchKernelGGL(kb_g_assemble, dim3(e.gasm, e.k), dim3(256), 0, s, dd,
+                       d + 1, r);
+}
+
+// The batched bodies: enqueue_solve_head / enqueue_tcg_iters /
+// enqueue_solve_tail / enqueue_eval_body for the fused dense chain, one
+// launch per stage. Linear, kernels only. fin: device array of the
+// members' IN fences, consumed by the first node.
+struct BatchShape { int d, r, max_inner; };
+
+static void enqueue_batch_tcg_iters(const BatchDesc* dd,
+                                    const BatchExtents& e,
+                                    const BatchShape& sh, int count,
+                                    hipStream_t s) {
+  for (int j = 0; j < count; ++j) {
+    launch_kb_hess<BH_HD, CF_ALPHA>(dd, e, sh.d, sh.r, TailArgs(), s);
+    hipLaunchKernelGGL((kb_tcg_update<CF_RR>), dim3(e.upd, e.k), dim3(256),
+                       0, s, dd);
+    launch_kb_precond(dd, e, sh.r, s);
+    launch_kb_proj<CF_BETA>(dd, e, sh.d, sh.r, s);
+  }
+}
+
+static void enqueue_batch_tail(const BatchDesc* dd, const BatchExtents& e,
+                               const BatchShape& sh, double accept_rho,
+                               hipStream_t s) {
+  launch_kb_candidate(dd, e, sh.d, sh.r, s);
+  TailArgs ta;
+  ta.a = accept_rho;
+  // last node: every agent's last block publishes its control block and
+  // releases its own F_SOLVE_OUT
+  launch_kb_hess<BH_CAND, CF_ACCEPT_OUT>(dd, e, sh.d, sh.r, ta, s);
+}
+
+static void enqueue_batch_solve(const BatchDesc* dd, const BatchExtents& e,
+                                const BatchShape& sh,
+                                unsigned int* const* fin, double tol,
+                                double Delta0, double accept_rho, int iters,
+                                hipStream_t s) {
+  hipLaunchKernelGGL(k_fence_wait_many, dim3(1), dim3(256), 0, s, fin, e.k);
+  launch_kb_gzero_assemble(dd, e, sh.d, sh.r, /*with_ctrl=*/true, s);
+  TailArgs ta;
+  ta.a = tol; ta.b = Delta0; ta.c = 1.0; ta.d = 0.1;
+  launch_kb_hess<BH_GRAD, CF_INIT>(dd, e, sh.d, sh.r, ta, s);
+  launch_kb_precond(dd, e, sh.r, s);
+  launch_kb_proj<CF_Z0>(dd, e, sh.d, sh.r, s);
+  enqueue_batch_tcg_iters(dd, e, sh, iters, s);
+  if (iters >= sh.max_inner)
+    hipLaunchKernelGGL(kb_ctrl_tcg_end, dim3(1, e.k), dim3(64), 0, s, dd);
+  enqueue_batch_tail(dd, e, sh, accept_rho, s);
+}
+
+static void enqueue_batch_cont(const BatchDesc* dd, const BatchExtents& e,
+                               const BatchShape& sh,
+                               unsigned int* const* fin, double accept_rho,
+                               int done, hipStream_t s) {
+  hipLaunchKernelGGL(k_fence_wait_many, dim3(1), dim3(256), 0, s, fin, e.k);
+  enqueue_batch_tcg_iters(dd, e, sh, sh.max_inner - done, s);
+  hipLaunchKernelGGL(kb_ctrl_tcg_end, dim3(1, e.k), dim3(64), 0, s, dd);
+  enqueue_batch_tail(dd, e, sh, accept_rho, s);
+}
+
+static void enqueue_batch_eval(const BatchDesc* dd, const BatchExtents& e,
+                               const BatchShape& sh,
+                               unsigned int* const* fin, hipStream_t s) {
+  hipLaunchKernelGGL(k_fence_wait_many, dim3(1), dim3(256), 0, s, fin, e.k);
+  launch_kb_gzero_assemble(dd, e, sh.d, sh.r, /*with_ctrl=*/false, s);
+  // every agent's last block writes its eval3 and releases F_EVAL_OUT
+  launch_kb_hess<BH_EVAL, CF_EVAL>(dd, e, sh.d, sh.r, TailArgs(), s);
+}
+
+// DPO_BATCH=0 forces the per-agent path everywhere.
+static bool batch_enabled() {
+  static const bool on = [] {
+    const char* v = getenv("DPO_BATCH");
+    return !(v && v[0] == '0');
+  }();
+  return on;
+}
+
+// An agent can be a member of a batch: fused dense chain, thread-per-pose
+// kernels, G assembled from a neighbour buffer.
+static bool batch_ctx_ok(const DpoCtx* c, const double* nbr) {
+  return c->Minv && ctx_fuse_scalar(c) && ctx_fold_delta(c) && nbr
+         && c->q_rp;
+}
+
+static void batch_fill_desc(BatchDesc& b, DpoCtx* c, double* X,
+                            const double* nbr) {
+  memset(&b, 0, sizeof(b));
+  b.q_rp = c->q_rp; b.q_ci = c->q_ci; b.q_vals = c->q_vals;
+  b.Minv = c->Minv;
+  b.g_E0 = c->g_E0; b.g_local_pose = c->g_local_pose;
+  b.g_nbr_slot = c->g_nbr_slot; b.g_w = c->g_w; b.g_ne = c->g_ne;
+  b.X = X; b.nbr = nbr;
+  b.Gt = ctx_bind_round_g(c);
+  b.G_buf = c->G_buf; b.grad = c->grad; b.eta = c->eta; b.delta = c->delta;
+  b.delta1 = c->delta1; b.rvec = c->rvec; b.z = c->z; b.Hd = c->Hd;
+  b.step = c->step; b.Xprop = c->Xprop; b.eta_snap = c->eta_snap;
+  b.delta_snap = c->delta_snap; b.ctrl = c->ctrl;
+  b.prezero_z = ctx_prezero_z(c);
+  b.ctrl_host_dev = c->ctrl_host_dev; b.eval3 = c->eval3;
+  b.fences = c->fences;
+  b.total = c->total; b.gtotal = c->g_ne > 0 ? c->total : 0;
+  b.n = c->n; b.N = c->N;
+  batch_desc_extents(b, c->dh, c->r);
+}
+
+extern "C" {
+
 // --- multi-agent round fan-out --------------------------------------
 // The distributed driver runs one rank per GPU; within a rank several
 // agents share the device. A round's per-agent enqueue loops (solve
@@ -3121,6 +3576,33 @@ __global__ void k_gather3_fenced(double* __restrict__ out, long stride,
   }
 }
 
+// One cached batch: the agents of an active id list (or, for the
+// evaluation, every agent of the group), their device descriptors and
+// fence lists, and the graphs of the batched sequences.
+#define BATCH_MAX_SOLVE 16  // members of a batched solve list
+#define BATCH_MAX_LISTS 16  // cached active lists (colored: one per colour)
+struct BatchSeq {
+  int k = 0;
+  int* ids = nullptr;
+  long* stamps = nullptr;  // the members' desc_stamp at the last build
+  bool built = false, ok = false;
+  BatchDesc* d_desc = nullptr;
+  unsigned int** d_fin = nullptr;   // members' IN fences
+  unsigned int** d_fout = nullptr;  // members' OUT fences
+  BatchExtents ext;
+  BatchShape sh = {0, 0, 0};
+  GraphCache primary, cont;
+  void release() {
+    primary.reset();
+    cont.reset();
+    dpo_ignore(hipFree(d_desc));
+    dpo_ignore(hipFree(d_fin));
+    dpo_ignore(hipFree(d_fout));
+    free(ids);
+    free(stamps);
+  }
+};
+
 struct DpoGroup {
   int n;
   DpoCtx** cs;
@@ -3130,11 +3612,123 @@ struct DpoGroup {
   int* d_rows;          // device array: output row per agent
   unsigned int** d_fin;   // device array: each ctx's F_EVAL_IN fence
   unsigned int** d_fout;  // device array: each ctx's F_EVAL_OUT fence
+  // batched path: one execution and one capture stream for the group
+  hipStream_t exec_stream = nullptr, cap_stream = nullptr;
+  hipEvent_t done_event = nullptr;
+  BatchSeq lists[BATCH_MAX_LISTS];
+  int n_lists = 0;
+  BatchSeq eval_seq;
+  BatchSeq* pending = nullptr;  // batched solve in flight (start .. finish)
+  double pend_rho = 0.0;
+  // counters: batched solve rounds, batched continuations, batched
+  // evaluations, per-agent solve rounds, per-agent evaluations, graph
+  // captures, descriptor builds
+  long n_bsolve = 0, n_bcont = 0, n_beval = 0, n_psolve = 0, n_peval = 0,
+       n_capture = 0, n_build = 0;
 };
+
+// (Re)build a batch when it is new or a member's descriptor stamp moved:
+// eligibility, descriptors, fence lists, extents; graphs are dropped
+// when the extents changed.
+// Returns whether the batch is eligible. eval selects the fence pair.
+static bool batch_seq_refresh(DpoGroup* gr, BatchSeq& q, bool eval) {
+  bool same = q.built;
+  for (int i = 0; same && i < q.k; ++i)
+    same = q.stamps[i] == gr->cs[q.ids[i]]->desc_stamp;
+  if (same) return q.ok;
+  // the old descriptors may still be in use by work on the group stream
+  DPO_CHECK(hipStreamSynchronize(gr->exec_stream));
+  const bool was_ok = q.built && q.ok;
+  const BatchExtents old_ext = q.ext;
+  const BatchShape old_sh = q.sh;
+  q.built = true;
+  q.ok = q.k >= 2;
+  const DpoCtx* c0 = gr->cs[q.ids[0]];
+  for (int i = 0; i < q.k; ++i) {
+    const DpoCtx* c = gr->cs[q.ids[i]];
+    q.stamps[i] = c->desc_stamp;
+    q.ok = q.ok && batch_ctx_ok(c, gr->nbrs[q.ids[i]]) && c->d == c0->d
+           && c->r == c0->r && c->max_inner == c0->max_inner;
+  }
+  if (!q.ok) {
+    q.primary.reset();
+    q.cont.reset();
+    return false;
+  }
+  gr->n_build++;
+  q.sh = {c0->d, c0->r, c0->max_inner};
+  BatchDesc* hd = (BatchDesc*)malloc(q.k * sizeof(BatchDesc));
+  unsigned int** hin = (unsigned int**)malloc(q.k * sizeof(void*));
+  unsigned int** hout = (unsigned int**)malloc(q.k * sizeof(void*));
+  q.ext = BatchExtents();
+  for (int i = 0; i < q.k; ++i) {
+    DpoCtx* c = gr->cs[q.ids[i]];
+    batch_fill_desc(hd[i], c, gr->Xs[q.ids[i]], gr->nbrs[q.ids[i]]);
+    q.ext.add(hd[i]);
+    hin[i] = c->fences + (eval ? F_EVAL_IN : F_SOLVE_IN);
+    hout[i] = c->fences + (eval ? F_EVAL_OUT : F_SOLVE_OUT);
+  }
+  if (!q.d_desc) {
+    DPO_CHECK(hipMalloc(&q.d_desc, q.k * sizeof(BatchDesc)));
+    DPO_CHECK(hipMalloc(&q.d_fin, q.k * sizeof(void*)));
+    DPO_CHECK(hipMalloc(&q.d_fout, q.k * sizeof(void*)));
+  }
+  DPO_CHECK(hipMemcpy(q.d_desc, hd, q.k * sizeof(BatchDesc),
+                      hipMemcpyHostToDevice));
+  DPO_CHECK(hipMemcpy(q.d_fin, hin, q.k * sizeof(void*),
+                      hipMemcpyHostToDevice));
+  DPO_CHECK(hipMemcpy(q.d_fout, hout, q.k * sizeof(void*),
+                      hipMemcpyHostToDevice));
+  free(hd); free(hin); free(hout);
+  // The graphs' kernels take the descriptor array (same allocation) and
+  // scalars as arguments, and their grids come from the extents: a member
+  // whose buffers moved but whose sizes did not (a preconditioner refresh
+  // allocates a new Minv) needs new descriptors, not a recapture.
+  if (!was_ok || memcmp(&old_ext, &q.ext, sizeof(old_ext)) != 0
+      || memcmp(&old_sh, &q.sh, sizeof(old_sh)) != 0) {
+    q.primary.reset();
+    q.cont.reset();
+  }
+  return true;
+}
+
+static void batch_seq_init(BatchSeq& q, const int* ids, int k) {
+  q.k = k;
+  q.ids = (int*)malloc(k * sizeof(int));
+  q.stamps = (long*)malloc(k * sizeof(long));
+  for (int i = 0; i < k; ++i) q.ids[i] = ids ? ids[i] : i;
+}
+
+// The cached batch of an active list; nullptr when the list cannot be
+// batched (the caller then takes the per-agent path).
+static BatchSeq* group_solve_batch(DpoGroup* gr, const int* ids, int k) {
+  static const bool no_graph = dpo_env_flag("DPO_NO_SOLVE_GRAPH");
+  if (!batch_enabled() || no_graph || k < 2 || k > BATCH_MAX_SOLVE)
+    return nullptr;
+  BatchSeq* q = nullptr;
+  for (int l = 0; l < gr->n_lists && !q; ++l)
+    if (gr->lists[l].k == k
+        && memcmp(gr->lists[l].ids, ids, k * sizeof(int)) == 0)
+      q = &gr->lists[l];
+  if (!q) {
+    if (gr->n_lists >= BATCH_MAX_LISTS) return nullptr;
+    for (int i = 0; i < k; ++i)
+      if (ids[i] < 0 || ids[i] >= gr->n) return nullptr;
+    q = &gr->lists[gr->n_lists++];
+    batch_seq_init(*q, ids, k);
+  }
+  return batch_seq_refresh(gr, *q, /*eval=*/false) ? q : nullptr;
+}
 
 void dpo_group_destroy(void* g) {
   DpoGroup* gr = (DpoGroup*)g;
   if (!gr) return;
+  if (gr->exec_stream) dpo_ignore(hipStreamSynchronize(gr->exec_stream));
+  for (int l = 0; l < gr->n_lists; ++l) gr->lists[l].release();
+  gr->eval_seq.release();
+  if (gr->exec_stream) dpo_ignore(hipStreamDestroy(gr->exec_stream));
+  if (gr->cap_stream) dpo_ignore(hipStreamDestroy(gr->cap_stream));
+  if (gr->done_event) dpo_ignore(hipEventDestroy(gr->done_event));
   dpo_ignore(hipFree(gr->d_srcs));
   dpo_ignore(hipFree(gr->d_rows));
   dpo_ignore(hipFree(gr->d_fin));
@@ -3174,60 +3768,267 @@ void* dpo_group_create(void** handles, int n, double** Xs,
   DPO_CHECK(hipMalloc(&gr->d_fout, n * sizeof(void*)));
   DPO_CHECK(hipMemcpy(gr->d_fout, fout_h, n * sizeof(void*),
                       hipMemcpyHostToDevice));
+  DPO_CHECK(hipStreamCreateWithFlags(&gr->exec_stream,
+                                     hipStreamNonBlocking));
+  DPO_CHECK(hipStreamCreateWithFlags(&gr->cap_stream, hipStreamNonBlocking));
+  DPO_CHECK(hipEventCreateWithFlags(&gr->done_event,
+                                    hipEventDisableTiming));
+  batch_seq_init(gr->eval_seq, nullptr, n);
   return gr;
 }
 
-// Fan-out solves for the active agents (indices into the group), on
-// each agent's private exec stream, fenced against join_stream.
+// Solves of the active agents (indices into the group).
+//
+// Batched (an eligible list, see group_solve_batch): one signal launch on
+// the join stream, one graph launch and one wait launch on the group's
+// stream. Otherwise the fan-out over each agent's private exec stream.
+//
+// The two paths may alternate from round to round. Ordering between them
+// always passes through the join stream: every IN fence is signalled
+// there, behind whatever the join stream has waited for, and every path
+// ends by making the join stream wait for its done event (solves) or its
+// OUT fences (evaluation). Neither path relies on the order of two
+// execution streams against each other.
 void dpo_group_solve_start(void* g, const int* ids, int k, double tol,
                            double Delta0, double accept_rho,
                            void* join_stream) {
   DpoGroup* gr = (DpoGroup*)g;
-  for (int i = 0; i < k; ++i) {
-    int a = ids[i];
-    dpo_round_solve_async(gr->cs[a], gr->Xs[a], gr->nbrs[a], tol, Delta0,
-                          accept_rho, join_stream);
+  hipStream_t js = (hipStream_t)join_stream;
+  BatchSeq* q = group_solve_batch(gr, ids, k);
+  gr->pending = q;
+  if (!q) {
+    gr->n_psolve++;
+    for (int i = 0; i < k; ++i) {
+      int a = ids[i];
+      dpo_round_solve_async(gr->cs[a], gr->Xs[a], gr->nbrs[a], tol, Delta0,
+                            accept_rho, join_stream);
+    }
+    return;
   }
+  gr->n_bsolve++;
+  gr->pend_rho = accept_rho;
+  for (int i = 0; i < k; ++i) ctx_bind_round_g(gr->cs[ids[i]]);
+  hipStream_t s = gr->exec_stream;
+  hipLaunchKernelGGL(k_fence_signal_many, dim3(1), dim3(256), 0, js,
+                     (unsigned int* const*)q->d_fin, q->k);
+  const int seg = solve_segment(gr->cs[ids[0]]);
+  const void* key[4] = {q->d_desc, (const void*)(intptr_t)(tol * 1e9),
+                        (const void*)(intptr_t)Delta0,
+                        (const void*)(intptr_t)(accept_rho * 1e9)};
+  const bool launched = graph_cache_launch(
+      q->primary, key, gr->cap_stream, s, [&](hipStream_t cs) {
+        gr->n_capture++;
+        enqueue_batch_solve(q->d_desc, q->ext, q->sh, q->d_fin, tol, Delta0,
+                            accept_rho, seg, cs);
+      });
+  if (!launched)  // capture unavailable: the whole sequence, eagerly
+    enqueue_batch_solve(q->d_desc, q->ext, q->sh, q->d_fin, tol, Delta0,
+                        accept_rho, q->sh.max_inner, s);
+  hipLaunchKernelGGL(k_fence_wait_many, dim3(1), dim3(256), 0, s,
+                     (unsigned int* const*)q->d_fout, q->k);
 }
 
 void dpo_group_solve_finish(void* g, const int* ids, int k,
                             int max_shrink, void* join_stream) {
   DpoGroup* gr = (DpoGroup*)g;
+  hipStream_t js = (hipStream_t)join_stream;
+  BatchSeq* q = gr->pending;
+  gr->pending = nullptr;
+  if (q) {
+    hipStream_t s = gr->exec_stream;
+    DPO_CHECK(hipStreamSynchronize(s));
+    // members still running get the rest of their iterations from the
+    // batched continuation. It runs for the whole list: the finished
+    // members' guarded kernels are no-ops, their unguarded publish step
+    // republishes and re-releases, so IN and OUT fences are handled the
+    // same for every member. (A member whose first candidate was rejected
+    // re-evaluates that same candidate; it then shrinks as usual.)
+    const int seg = solve_segment(gr->cs[ids[0]]);
+    bool any_run = false;
+    if (seg < q->sh.max_inner)
+      for (int i = 0; i < k; ++i) {
+        DpoCtx* c = gr->cs[ids[i]];
+        if ((int)c->ctrl_host[C_STATUS] == ST_RUN) {
+          c->n_conts++;
+          any_run = true;
+        }
+      }
+    if (any_run) {
+      gr->n_bcont++;
+      hipLaunchKernelGGL(k_fence_signal_many, dim3(1), dim3(256), 0, s,
+                         (unsigned int* const*)q->d_fin, q->k);
+      const void* key[4] = {q->d_desc, nullptr, nullptr,
+                            (const void*)(intptr_t)(gr->pend_rho * 1e9)};
+      const bool launched = graph_cache_launch(
+          q->cont, key, gr->cap_stream, s, [&](hipStream_t cs) {
+            gr->n_capture++;
+            enqueue_batch_cont(q->d_desc, q->ext, q->sh, q->d_fin,
+                               gr->pend_rho, seg, cs);
+          });
+      if (!launched)
+        enqueue_batch_cont(q->d_desc, q->ext, q->sh, q->d_fin, gr->pend_rho,
+                           seg, s);
+      hipLaunchKernelGGL(k_fence_wait_many, dim3(1), dim3(256), 0, s,
+                         (unsigned int* const*)q->d_fout, q->k);
+      DPO_CHECK(hipStreamSynchronize(s));
+    }
+    // acceptance, the (rare) shrink loop and the counters per agent, on
+    // the group's stream; then one launch commits X <- Xprop for every
+    // member that ended accepted
+    unsigned int mask = 0;
+    for (int i = 0; i < k; ++i) {
+      DpoCtx* c = gr->cs[ids[i]];
+      const int st = solve_postsync(c, gr->Xs[ids[i]], gr->pend_rho,
+                                    max_shrink, 0, nullptr, s,
+                                    /*commit=*/false);
+      if (st == ST_ACCEPTED) mask |= 1u << i;
+    }
+    if (mask)
+      hipLaunchKernelGGL(kb_commit, dim3(q->ext.copy, q->k), dim3(256), 0, s,
+                         q->d_desc, mask);
+    DPO_CHECK(hipEventRecord(gr->done_event, s));
+    DPO_CHECK(hipStreamWaitEvent(js, gr->done_event, 0));
+    return;
+  }
   bool continued[256];  // dpo_group_create caps a group at 256 agents
   // pass 1: an agent that needs no continuation is finished at once, as
   // before; one that does only gets its continuation launched
   for (int i = 0; i < k && i < 256; ++i) {
     continued[i] = round_finish_primary(gr->cs[ids[i]]);
     if (!continued[i])
-      round_finish_post(gr->cs[ids[i]], false, max_shrink, nullptr,
-                        (hipStream_t)join_stream);
+      round_finish_post(gr->cs[ids[i]], false, max_shrink, nullptr, js);
   }
   // pass 2: the continued agents
   for (int i = 0; i < k && i < 256; ++i)
     if (continued[i])
-      round_finish_post(gr->cs[ids[i]], true, max_shrink, nullptr,
-                        (hipStream_t)join_stream);
+      round_finish_post(gr->cs[ids[i]], true, max_shrink, nullptr, js);
 }
 
-// Fan-out evaluation of EVERY agent in the group into its eval3
-// scratch (per-agent exec streams, fenced), then gather all rows into
-// out_dev[rows[i]*row_stride .. +3] with one kernel on join_stream.
+// Evaluation of EVERY agent in the group into its eval3 scratch, then
+// all rows gathered into out_dev[rows[i]*row_stride .. +3] with one
+// kernel on join_stream. Batched (every agent eligible): one signal
+// launch, one graph launch on the group's stream, the gather. Otherwise
+// the fan-out over the per-agent exec streams.
 void dpo_group_eval(void* g, double* out_dev, long row_stride,
                     void* join_stream) {
   DpoGroup* gr = (DpoGroup*)g;
   hipStream_t js = (hipStream_t)join_stream;
+  static const bool no_graph = dpo_env_flag("DPO_NO_EVAL_GRAPH");
+  const bool batched = batch_enabled() && !no_graph
+                       && batch_seq_refresh(gr, gr->eval_seq, /*eval=*/true);
   // one kernel signals every agent's IN fence (carries the boundary
-  // scatter ordering); the per-agent eval graphs are then launched
-  // bare on their exec streams — no event ceremony — and one gather
-  // kernel on the join stream waits on & consumes every OUT fence.
+  // scatter ordering); the evaluation graphs are then launched bare on
+  // their exec streams — no event ceremony — and one gather kernel on the
+  // join stream waits on & consumes every OUT fence.
   hipLaunchKernelGGL(k_fence_signal_many, dim3(1), dim3(256), 0, js,
                      (unsigned int* const*)gr->d_fin, gr->n);
-  for (int i = 0; i < gr->n; ++i)
-    round_eval_impl(gr->cs[i], gr->Xs[i], gr->nbrs[i], gr->cs[i]->eval3,
-                    gr->cs[i]->exec_stream, /*wait_out=*/false);
+  if (batched) {
+    BatchSeq& q = gr->eval_seq;
+    gr->n_beval++;
+    for (int i = 0; i < gr->n; ++i) ctx_bind_round_g(gr->cs[i]);
+    const void* key[4] = {q.d_desc, nullptr, nullptr, nullptr};
+    const bool launched = graph_cache_launch(
+        q.primary, key, gr->cap_stream, gr->exec_stream,
+        [&](hipStream_t cs) {
+          gr->n_capture++;
+          enqueue_batch_eval(q.d_desc, q.ext, q.sh, q.d_fin, cs);
+        });
+    if (!launched)
+      enqueue_batch_eval(q.d_desc, q.ext, q.sh, q.d_fin, gr->exec_stream);
+  } else {
+    gr->n_peval++;
+    for (int i = 0; i < gr->n; ++i)
+      round_eval_impl(gr->cs[i], gr->Xs[i], gr->nbrs[i], gr->cs[i]->eval3,
+                      gr->cs[i]->exec_stream, /*wait_out=*/false);
+  }
   hipLaunchKernelGGL(k_gather3_fenced, dim3(1), dim3(256), 0, js,
                      out_dev, row_stride, gr->d_srcs, gr->d_rows,
                      (unsigned int* const*)gr->d_fout, gr->n);
+}
+
+// out[0..6] = batched solve rounds, batched continuations, batched
+// evaluations, per-agent solve rounds, per-agent evaluations, graph
+// captures of the batched sequences, descriptor builds. Writes at most
+// `cap` entries; returns the full length.
+int dpo_group_counters(void* g, long* out, int cap) {
+  DpoGroup* gr = (DpoGroup*)g;
+  const long v[7] = {gr->n_bsolve, gr->n_bcont, gr->n_beval, gr->n_psolve,
+                     gr->n_peval, gr->n_capture, gr->n_build};
+  for (int i = 0; i < 7 && i < cap; ++i) out[i] = v[i];
+  return 7;
+}
+
+// --- the batched wrappers as stand-alone ops (tests) -----------------
+// Test support, like dpo_hd_stage / dpo_candidate / dpo_hess_tail above:
+// nothing in the package calls these two.
+int dpo_batch_desc_size() { return (int)sizeof(BatchDesc); }
+
+// One batched wrapper on caller-owned descriptors (tests): descs_host is
+// an array of k BatchDesc whose pointer fields are set; the extents are
+// filled in here. Uploads, launches on `stream` and synchronises.
+//   0 kb_dzero          1 kb_dzero2        2 kb_g_assemble
+//   3 gradient + CF_INIT (a = tol, b = Delta0)
+//   4 folded Hd + CF_ALPHA
+//   5 candidate evaluation + CF_ACCEPT_OUT (a = accept_rho)
+//   6 candidate evaluation + CF_ACCEPT     (a = accept_rho)
+//   7 evaluation + CF_EVAL
+//   8 kb_precond_dense  9 kb_proj_dots CF_Z0   10 kb_proj_dots CF_BETA
+//  11 kb_tcg_update CF_RR   12 kb_candidate    13 kb_ctrl_tcg_end
+//  14 kb_commit (mask = (unsigned)a)
+int dpo_batch_op(int op, void* descs_host, int k, int d, int r, double a,
+                 double b, void* stream) {
+  if (k <= 0 || k > 32) return -1;
+  hipStream_t s = (hipStream_t)stream;
+  BatchDesc* hd = (BatchDesc*)descs_host;
+  BatchExtents e;
+  for (int i = 0; i < k; ++i) {
+    batch_desc_extents(hd[i], d + 1, r);
+    e.add(hd[i]);
+  }
+  BatchDesc* dd = nullptr;
+  DPO_CHECK(hipMalloc(&dd, k * sizeof(BatchDesc)));
+  DPO_CHECK(hipMemcpy(dd, hd, k * sizeof(BatchDesc), hipMemcpyHostToDevice));
+  TailArgs ta;
+  ta.a = a; ta.b = b; ta.c = 1.0; ta.d = 0.1;
+  int rc = 0;
+  switch (op) {
+    case 0:
+      if (e.zero > 0)
+        hipLaunchKernelGGL(kb_dzero, dim3(e.zero, k), dim3(256), 0, s, dd);
+      break;
+    case 1:
+      hipLaunchKernelGGL(kb_dzero2, dim3(e.zero2, k), dim3(256), 0, s, dd);
+      break;
+    case 2:
+      if (e.gasm > 0)
+        hipLaunchKernelGGL(kb_g_assemble, dim3(e.gasm, k), dim3(256), 0, s,
+                           dd, d + 1, r);
+      break;
+    case 3: launch_kb_hess<BH_GRAD, CF_INIT>(dd, e, d, r, ta, s); break;
+    case 4: launch_kb_hess<BH_HD, CF_ALPHA>(dd, e, d, r, ta, s); break;
+    case 5: launch_kb_hess<BH_CAND, CF_ACCEPT_OUT>(dd, e, d, r, ta, s); break;
+    case 6: launch_kb_hess<BH_CAND, CF_ACCEPT>(dd, e, d, r, ta, s); break;
+    case 7: launch_kb_hess<BH_EVAL, CF_EVAL>(dd, e, d, r, ta, s); break;
+    case 8: launch_kb_precond(dd, e, r, s); break;
+    case 9: launch_kb_proj<CF_Z0>(dd, e, d, r, s); break;
+    case 10: launch_kb_proj<CF_BETA>(dd, e, d, r, s); break;
+    case 11:
+      hipLaunchKernelGGL((kb_tcg_update<CF_RR>), dim3(e.upd, k), dim3(256),
+                         0, s, dd);
+      break;
+    case 12: launch_kb_candidate(dd, e, d, r, s); break;
+    case 13:
+      hipLaunchKernelGGL(kb_ctrl_tcg_end, dim3(1, k), dim3(64), 0, s, dd);
+      break;
+    case 14:
+      hipLaunchKernelGGL(kb_commit, dim3(e.copy, k), dim3(256), 0, s, dd,
+                         (unsigned int)a);
+      break;
+    default: rc = -1; break;
+  }
+  DPO_CHECK(hipStreamSynchronize(s));
+  dpo_ignore(hipFree(dd));
+  return rc;
 }
 
 }  // extern "C"

@@ -83,6 +83,11 @@ _lib.dpo_group_solve_start.argtypes = [
 _lib.dpo_group_solve_finish.argtypes = [
     _c, ctypes.POINTER(ctypes.c_int), _i, _i, _c]
 _lib.dpo_group_eval.argtypes = [_c, _c, _l, _c]
+_lib.dpo_group_counters.restype = _i
+_lib.dpo_group_counters.argtypes = [_c, ctypes.POINTER(ctypes.c_long), _i]
+_lib.dpo_batch_desc_size.restype = _i
+_lib.dpo_batch_op.restype = _i
+_lib.dpo_batch_op.argtypes = [_i, _c, _i, _i, _i, _d, _d, _c]
 _lib.dpo_ctx_ctrl.restype = _i
 _lib.dpo_ctx_ctrl.argtypes = [_c, ctypes.POINTER(ctypes.c_double), _i]
 _lib.dpo_hd_stage.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c, _i, _i,
@@ -634,6 +639,16 @@ class DeviceGroup:
     def solve_finish(self, ids, max_shrink: int = 10) -> None:
         _lib.dpo_group_solve_finish(self.handle, ids, len(ids),
                                     max_shrink, _stream(self._js_of))
+
+    def counters(self) -> dict:
+        """Which path the group's rounds took: batched / per-agent solve
+        rounds and evaluations, batched continuations, graph captures of
+        the batched sequences and descriptor builds."""
+        buf = (ctypes.c_long * 7)()
+        assert _lib.dpo_group_counters(self.handle, buf, 7) == 7
+        keys = ("batched_solves", "batched_conts", "batched_evals",
+                "agent_solves", "agent_evals", "captures", "desc_builds")
+        return {k: int(v) for k, v in zip(keys, buf)}
 
     def eval_all(self, out: Tensor) -> None:
         """Evaluate every agent; out is a (num_robots, 3) fp64 device
