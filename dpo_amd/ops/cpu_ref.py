@@ -517,3 +517,153 @@ def round_cost(Q, X: Tensor, G: Optional[Tensor] = None) -> Tensor:
     if G is not None:
         f = f + (X * G).sum()
     return f.reshape(1)
+
+
+# ---------------------------------------------------------------------
+# Certificate, second eigensolver: LOBPCG with a Gram-based
+# Rayleigh-Ritz step (docs/DESIGN.md §20). The control array mirrors
+# LobSlot in dpo_ops.hip; the functions below are the fp64 reference of
+# the HIP ops. Blocks are row-major (N, m); B = [X W P] and SB = [SX SW
+# SP] are (3, N, m) tensors.
+# ---------------------------------------------------------------------
+LOB_STATUS, LOB_THETA, LOB_COEF = 0, 4, 12
+LOB_MAX_M = 8
+LOB_SIZE = LOB_COEF + (3 * LOB_MAX_M) * (2 * LOB_MAX_M)
+LOB_X, LOB_W, LOB_P = 0, 1, 2           # block numbers inside B and SB
+# partial slots of the HIP kernels: Gram tiles, then residual columns
+LOB_GPART = 24 * LOB_MAX_M * 4 * CERT_BLOCK
+LOB_RPART = LOB_MAX_M * CERT_BLOCK
+
+
+class LobWorkspace:
+    """Caller-owned buffers of one LOBPCG run with block size m: B and SB
+    (3, N, m), the residual block R (N, m) (seven blocks in all), the
+    control array, the partial slots and `out` = [G_B (3m, 3m), G_A
+    (3m, 3m), squared residual norms (m)], which the host reads once per
+    iteration."""
+
+    def __init__(self, N: int, m: int, device="cpu"):
+        if not 1 <= m <= LOB_MAX_M:
+            raise ValueError(f"block size {m} outside 1..{LOB_MAX_M}")
+        kw = dict(dtype=torch.float64, device=device)
+        self.N, self.m = N, m
+        self.B = torch.zeros(3, N, m, **kw)
+        self.SB = torch.zeros(3, N, m, **kw)
+        self.R = torch.zeros(N, m, **kw)
+        self.ctl = torch.zeros(LOB_SIZE, **kw)
+        self.part = torch.zeros(LOB_GPART + LOB_RPART, **kw)
+        self.out = torch.zeros(2 * 9 * m * m + m, **kw)
+
+    def unpack(self, h=None):
+        """(G_B, G_A, rn2) as numpy arrays from `out` (or a host copy h),
+        G_B and G_A symmetrised from their upper triangles."""
+        import numpy as np
+        if h is None:
+            h = self.out.cpu().numpy()
+        k = 3 * self.m
+        mats = []
+        for a in range(2):
+            U = np.triu(h[a * k * k:(a + 1) * k * k].reshape(k, k))
+            mats.append(U + np.triu(U, 1).T)
+        return mats[0], mats[1], h[2 * k * k:].copy()
+
+
+def lob_set_coefficients(ctl_host: Tensor, theta, C, m: int) -> None:
+    """Fill a host copy of the control array: theta (m) and C (3m, 2m)."""
+    ctl_host[LOB_THETA:LOB_THETA + m] = torch.as_tensor(
+        theta, dtype=torch.float64)
+    ctl_host[LOB_COEF:LOB_COEF + 6 * m * m] = torch.as_tensor(
+        C, dtype=torch.float64).reshape(-1)
+
+
+def _lob_run(ws: LobWorkspace) -> bool:
+    return float(ws.ctl[LOB_STATUS]) == 0.0
+
+
+def cert_lob_resid(ws: LobWorkspace, zero: bool = False) -> None:
+    """R = SX - X diag(theta) and the squared column norms, left in the
+    residual slots of ws.part (slot 0 of each column here; per-block
+    partials on the device). `zero` clears W."""
+    if not _lob_run(ws):
+        return
+    m = ws.m
+    theta = ws.ctl[LOB_THETA:LOB_THETA + m]
+    torch.sub(ws.SB[LOB_X], ws.B[LOB_X] * theta, out=ws.R)
+    npart = cert_partials(ws.N)
+    rp = ws.part[LOB_GPART:LOB_GPART + m * npart].view(m, npart)
+    rp.zero_()
+    rp[:, 0] = (ws.R * ws.R).sum(dim=0)
+    if zero:
+        ws.B[LOB_W].zero_()
+
+
+def lob_precond(pre, V: Tensor, d: int) -> Tensor:
+    """T V for pre = (mode, data) as in `_refine_precond`, without the
+    tangent projection: the eigenproblem lives in R^N."""
+    mode, data = pre
+    N, m = V.shape
+    if mode == "jacobi":
+        Z = torch.cholesky_solve(V.view(N // (d + 1), d + 1, m), data)
+        return Z.reshape(N, m)
+    if mode == "dense":
+        return data.to(torch.float64) @ V
+    if mode == "exact":
+        return torch.from_numpy(data.solve(V.numpy()))
+    raise ValueError(f"unknown preconditioner mode {mode!r}")
+
+
+def cert_lob_precond(ws: LobWorkspace, pre, d: int) -> None:
+    """W = T R."""
+    if _lob_run(ws):
+        ws.B[LOB_W].copy_(lob_precond(pre, ws.R, d))
+
+
+def cert_lob_apply(Q, lam: Tensor, ws: LobWorkspace, blk: int) -> None:
+    """SB[blk] = (Q - Lambda) B[blk]."""
+    if not _lob_run(ws):
+        return
+    n, d = lam.shape[0], lam.shape[1]
+    V = ws.B[blk]
+    out = torch.sparse.mm(Q.to_scalar_csr(), V)
+    ob = out.view(n, d + 1, ws.m)
+    ob[:, :d, :] -= torch.bmm(lam, V.view(n, d + 1, ws.m)[:, :d, :])
+    ws.SB[blk].copy_(out)
+
+
+def cert_lob_gram(ws: LobWorkspace) -> None:
+    """out = [B^T B, B^T SB, squared residual norms]."""
+    if not _lob_run(ws):
+        return
+    m, k = ws.m, 3 * ws.m
+    Bf = ws.B.permute(1, 0, 2).reshape(ws.N, k)
+    SBf = ws.SB.permute(1, 0, 2).reshape(ws.N, k)
+    ws.out[:k * k] = (Bf.T @ Bf).reshape(-1)
+    ws.out[k * k:2 * k * k] = (Bf.T @ SBf).reshape(-1)
+    npart = cert_partials(ws.N)
+    rp = ws.part[LOB_GPART:LOB_GPART + m * npart].view(m, npart)
+    ws.out[2 * k * k:] = rp.sum(dim=1)
+
+
+def cert_lob_update(ws: LobWorkspace) -> None:
+    """X <- [X W P] C[:, :m], P <- [W P] C[m:, m:], and SX, SP from SB
+    with the same coefficients (out of place, then stored)."""
+    if not _lob_run(ws):
+        return
+    m, k = ws.m, 3 * ws.m
+    C = ws.ctl[LOB_COEF:LOB_COEF + k * 2 * m].view(k, 2 * m)
+    for T in (ws.B, ws.SB):
+        Tf = T.permute(1, 0, 2).reshape(ws.N, k)
+        newx = Tf @ C[:, :m]
+        newp = Tf[:, m:] @ C[m:, m:]
+        T[LOB_X].copy_(newx)
+        T[LOB_P].copy_(newp)
+
+
+def cert_lob_iter(Q, lam: Tensor, ws: LobWorkspace, pre) -> None:
+    """The device half of one iteration: residual, W = T R, SW = S W and
+    the Gram matrices."""
+    d = lam.shape[1]
+    cert_lob_resid(ws, zero=pre[0] == "dense")
+    cert_lob_precond(ws, pre, d)
+    cert_lob_apply(Q, lam, ws, LOB_W)
+    cert_lob_gram(ws)

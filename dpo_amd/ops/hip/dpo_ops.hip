@@ -5328,3 +5328,369 @@ void dpo_round_gauge(double* Xr, double* traj, const double* anchor, int n,
 }
 
 }  // extern "C"
+
+// =====================================================================
+// Certificate, second eigensolver: LOBPCG with a Gram-based
+// Rayleigh-Ritz step (docs/DESIGN.md §20). Blocks are row-major (N, m)
+// like Xt, m one of the compiled r, so k_precond_dense<m> and
+// k_precond_jacobi serve unchanged. B = [X W P] and SB = [SX SW SP] are
+// three contiguous (N, m) blocks each.
+//
+// One iteration on the device: k_lob_resid (R = SX - X diag(theta),
+// clears W for the dense apply), the preconditioner W = T R,
+// k_lob_apply (SW = Q W - Lambda W), k_lob_gram + k_lob_gram_finish
+// (B^T B, B^T SB and the m squared residual norms into `out`). The host
+// reads `out`, solves the (3m) x (3m) pencil and uploads theta and the
+// coefficients into the control array; k_lob_update forms the new X, P,
+// SX, SP in place.
+//
+// House rules of the certificate section: CERT_BS threads, cert_grid,
+// per-block partials in fixed slots summed by cert_sum_partials in a
+// later launch, no floating-point atomics in any kernel here. Control
+// array `lc`: status in slot 0 (0 = run; anything else turns every
+// kernel, the reused preconditioner kernels included, into a no-op).
+// =====================================================================
+enum LobSlot {
+  LB_STATUS = 0,
+  LB_THETA = 4,    // theta[j] at LB_THETA + j, j < LOB_MAX_M
+  LB_COEF = 12,    // (3m) x (2m) row-major: columns [0, m) give the new
+                   // X, columns [m, 2m) the new P (rows [0, m) unused)
+  LB_SIZE = 12 + 24 * 16,
+};
+#define LOB_MAX_M DPO_MAX_R
+#define LOB_GT 4     // columns of the right operand per Gram tile
+#define LOB_PAIRS 6  // block pairs (p <= q) of a 3 x 3 block matrix
+// Gram tiles: 2 matrices x LOB_PAIRS x ceil(m / LOB_GT) chunks, each with
+// m x LOB_GT accumulators (at most 32) and one partial per block
+#define LOB_MAX_TILES (2 * LOB_PAIRS * ((LOB_MAX_M + LOB_GT - 1) / LOB_GT))
+#define LOB_GPART (LOB_MAX_TILES * LOB_MAX_M * LOB_GT * CERT_MAX_PART)
+#define LOB_RPART (LOB_MAX_M * CERT_MAX_PART)
+
+__device__ __forceinline__ bool lob_off(const double* lc) {
+  return lc[LB_STATUS] != 0.0;
+}
+
+// R = SX - X diag(theta), one thread per row; rpart[j * grid + block] =
+// block partial of ||R[:, j]||^2. zero != nullptr: that (N, m) block is
+// cleared (the j-split partial sums of k_precond_dense accumulate there).
+template <int M>
+__global__ void __launch_bounds__(CERT_BS)
+k_lob_resid(const double* __restrict__ lc, const double* __restrict__ X,
+            const double* __restrict__ SX, double* __restrict__ R,
+            double* __restrict__ zero, double* __restrict__ rpart, long N) {
+  if (lob_off(lc)) return;
+  double th[M], nrm[M];
+  #pragma unroll
+  for (int j = 0; j < M; ++j) {
+    th[j] = lc[LB_THETA + j];
+    nrm[j] = 0.0;
+  }
+  for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+       row += (long)gridDim.x * CERT_BS) {
+    const size_t o = (size_t)row * M;
+    #pragma unroll
+    for (int j = 0; j < M; ++j) {
+      const double rv = fma(-th[j], X[o + j], SX[o + j]);
+      R[o + j] = rv;
+      nrm[j] = fma(rv, rv, nrm[j]);
+      if (zero != nullptr) zero[o + j] = 0.0;
+    }
+  }
+  #pragma unroll
+  for (int j = 0; j < M; ++j) {
+    const double s = cert_block_sum(nrm[j]);
+    if (threadIdx.x == 0) rpart[(size_t)j * gridDim.x + blockIdx.x] = s;
+  }
+}
+
+// SW = Q W - Lambda W for M columns in one pass: the BSR traversal of
+// k_bsr_spmm (one thread per element of a pose's (D+1) x M tile, grid
+// stride over poses) and the d x d Lambda correction of k_cert_apply.
+template <int D, int M>
+__global__ void __launch_bounds__(CERT_BS)
+k_lob_apply(const double* __restrict__ lc, const int* __restrict__ row_ptr,
+            const int* __restrict__ col_idx, const double* __restrict__ vals,
+            const double* __restrict__ lam, const double* __restrict__ W,
+            double* __restrict__ SW, int n) {
+  if (lob_off(lc)) return;
+  constexpr int DH = D + 1;
+  constexpr int tile = DH * M;
+  constexpr int per_block = CERT_BS / tile;
+  const int slot = threadIdx.x / tile;
+  const int t = threadIdx.x % tile;
+  if (slot >= per_block) return;
+  const int c = t / M;  // row inside the pose block
+  const int k = t % M;  // column of W
+  for (long i = (long)blockIdx.x * per_block + slot; i < n;
+       i += (long)gridDim.x * per_block) {
+    const int s = row_ptr[i], e = row_ptr[i + 1];
+    double acc = 0.0;
+    for (int p = s; p < e; ++p) {
+      const double* Bq = vals + (size_t)p * DH * DH + c * DH;
+      const double* Wj = W + (size_t)col_idx[p] * tile;
+      #pragma unroll
+      for (int cc = 0; cc < DH; ++cc) acc = fma(Bq[cc], Wj[cc * M + k], acc);
+    }
+    if (c < D) {
+      const double* Li = lam + (size_t)i * D * D + c * D;
+      const double* Wi = W + (size_t)i * tile;
+      #pragma unroll
+      for (int b = 0; b < D; ++b) acc = fma(-Li[b], Wi[b * M + k], acc);
+    }
+    SW[(size_t)i * tile + c * M + k] = acc;
+  }
+}
+
+// Block pair (p <= q) number `pair` of the upper block triangle.
+__device__ __forceinline__ void lob_pair(int pair, int& p, int& q) {
+  p = pair < 3 ? 0 : (pair < 5 ? 1 : 2);
+  q = pair < 3 ? pair : (pair < 5 ? pair - 2 : 2);
+}
+
+// Row-split Gram tiles of G_B = B^T B (which = 0) and G_A = B^T SB
+// (which = 1). blockIdx.y = (which * LOB_PAIRS + pair) * NCH + chunk
+// selects the M x LOB_GT tile: all M columns of block p against columns
+// [chunk * LOB_GT, +LOB_GT) of block q of B or SB. A tail chunk clamps
+// the column and the finish kernel discards the duplicates. One partial
+// per (tile entry, block) at gpart[((y * M + a) * LOB_GT + c) * grid + b].
+template <int M>
+__global__ void __launch_bounds__(CERT_BS)
+k_lob_gram(const double* __restrict__ lc, const double* __restrict__ B,
+           const double* __restrict__ SB, double* __restrict__ gpart,
+           long N) {
+  if (lob_off(lc)) return;
+  constexpr int NCH = (M + LOB_GT - 1) / LOB_GT;
+  const int y = blockIdx.y;
+  const int chunk = y % NCH;
+  const int which = y / (NCH * LOB_PAIRS);
+  int p, q;
+  lob_pair((y / NCH) % LOB_PAIRS, p, q);
+  const double* L = B + (size_t)p * N * M;
+  const double* Rt = (which ? SB : B) + (size_t)q * N * M;
+  int col[LOB_GT];
+  #pragma unroll
+  for (int c = 0; c < LOB_GT; ++c) {
+    const int cc = chunk * LOB_GT + c;
+    col[c] = cc < M ? cc : M - 1;
+  }
+  double acc[M][LOB_GT];
+  #pragma unroll
+  for (int a = 0; a < M; ++a)
+    #pragma unroll
+    for (int c = 0; c < LOB_GT; ++c) acc[a][c] = 0.0;
+  for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+       row += (long)gridDim.x * CERT_BS) {
+    const size_t o = (size_t)row * M;
+    double rv[LOB_GT];
+    #pragma unroll
+    for (int c = 0; c < LOB_GT; ++c) rv[c] = Rt[o + col[c]];
+    #pragma unroll
+    for (int a = 0; a < M; ++a) {
+      const double lv = L[o + a];
+      #pragma unroll
+      for (int c = 0; c < LOB_GT; ++c) acc[a][c] = fma(lv, rv[c], acc[a][c]);
+    }
+  }
+  #pragma unroll
+  for (int a = 0; a < M; ++a)
+    #pragma unroll
+    for (int c = 0; c < LOB_GT; ++c) {
+      const double s = cert_block_sum(acc[a][c]);
+      if (threadIdx.x == 0)
+        gpart[((size_t)(y * M + a) * LOB_GT + c) * gridDim.x + blockIdx.x] =
+            s;
+    }
+}
+
+// One workgroup per Gram tile entry, then one per residual column: the
+// fixed-order sum of its ngrid partials. out: G_B (3m x 3m, row-major),
+// G_A (the same), then the m squared residual norms. Only entries
+// (row, col) of block pairs p <= q are written: the upper triangles are
+// complete, the rest of `out` is left as it was.
+__global__ void __launch_bounds__(CERT_BS)
+k_lob_gram_finish(const double* __restrict__ lc,
+                  const double* __restrict__ gpart,
+                  const double* __restrict__ rpart, int ngrid, int m,
+                  double* __restrict__ out) {
+  if (lob_off(lc)) return;
+  const int nslot = (int)gridDim.x - m;
+  const int b = blockIdx.x;
+  const int k3 = 3 * m;
+  if (b >= nslot) {
+    const int j = b - nslot;
+    const double s = cert_sum_partials(rpart + (size_t)j * ngrid, ngrid);
+    if (threadIdx.x == 0) out[2 * k3 * k3 + j] = s;
+    return;
+  }
+  const int nch = (m + LOB_GT - 1) / LOB_GT;
+  const int c = b % LOB_GT;
+  const int a = (b / LOB_GT) % m;
+  const int y = b / (LOB_GT * m);
+  const int cc = (y % nch) * LOB_GT + c;
+  if (cc >= m) return;  // clamped duplicate of a tail chunk
+  const int which = y / (nch * LOB_PAIRS);
+  int p, q;
+  lob_pair((y / nch) % LOB_PAIRS, p, q);
+  const double s = cert_sum_partials(gpart + (size_t)b * ngrid, ngrid);
+  if (threadIdx.x == 0)
+    out[which * k3 * k3 + (p * m + a) * k3 + q * m + cc] = s;
+}
+
+// In-place update with the coefficients C at lc + LB_COEF, one thread per
+// row: X <- [X W P] C[:, :M], P <- [W P] C[M:, M:], and SX, SP from SB
+// with the same coefficients. A thread loads all 3M values of B and of SB
+// of its row before its first store and no other thread touches that
+// row, so in place is safe (the k_cert_contract argument). B and SB are
+// deliberately not __restrict__: the stores alias the loads.
+template <int M>
+__global__ void __launch_bounds__(CERT_BS)
+k_lob_update(const double* __restrict__ lc, double* B, double* SB, long N) {
+  if (lob_off(lc)) return;
+  const double* __restrict__ C = lc + LB_COEF;
+  const size_t blk = (size_t)N * M;
+  for (long row = (long)blockIdx.x * CERT_BS + threadIdx.x; row < N;
+       row += (long)gridDim.x * CERT_BS) {
+    const size_t o = (size_t)row * M;
+    double b[3 * M], sb[3 * M];
+    #pragma unroll
+    for (int g = 0; g < 3; ++g)
+      #pragma unroll
+      for (int j = 0; j < M; ++j) {
+        b[g * M + j] = B[g * blk + o + j];
+        sb[g * M + j] = SB[g * blk + o + j];
+      }
+    #pragma unroll
+    for (int j = 0; j < M; ++j) {
+      double x = 0.0, sx = 0.0, pn = 0.0, sp = 0.0;
+      #pragma unroll
+      for (int k = 0; k < 3 * M; ++k) {
+        const double cx = C[k * 2 * M + j];
+        x = fma(cx, b[k], x);
+        sx = fma(cx, sb[k], sx);
+        if (k >= M) {
+          const double cp = C[k * 2 * M + M + j];
+          pn = fma(cp, b[k], pn);
+          sp = fma(cp, sb[k], sp);
+        }
+      }
+      B[o + j] = x;
+      SB[o + j] = sx;
+      B[2 * blk + o + j] = pn;
+      SB[2 * blk + o + j] = sp;
+    }
+  }
+}
+
+static void lob_bad_block(int m) {
+  fprintf(stderr, "dpo_ops: unsupported LOBPCG block size m=%d\n", m);
+  abort();
+}
+
+static void launch_lob_resid(const double* lc, const double* X,
+                             const double* SX, double* R, double* zero,
+                             double* rpart, long N, int m, hipStream_t s) {
+  if (!dispatch_r(m, [&](auto Mc) {
+        hipLaunchKernelGGL((k_lob_resid<Mc>), dim3(cert_grid(N)),
+                           dim3(CERT_BS), 0, s, lc, X, SX, R, zero, rpart,
+                           N);
+      }))
+    lob_bad_block(m);
+}
+
+static void launch_lob_apply(const double* lc, const int* rp, const int* ci,
+                             const double* vals, const double* lam,
+                             const double* W, double* SW, int n, int d,
+                             int m, hipStream_t s) {
+  const int per_block = CERT_BS / ((d + 1) * m);
+  const int grid = cert_grid((long)blocks_for(n, per_block) * CERT_BS);
+  if (!dispatch_dr(d, m, [&](auto Dc, auto Mc) {
+        hipLaunchKernelGGL((k_lob_apply<Dc, Mc>), dim3(grid), dim3(CERT_BS),
+                           0, s, lc, rp, ci, vals, lam, W, SW, n);
+      }))
+    dpo_bad_shape(d, m);
+}
+
+static void launch_lob_gram(const double* lc, const double* B,
+                            const double* SB, double* gpart,
+                            const double* rpart, double* out, long N, int m,
+                            hipStream_t s) {
+  const int grid = cert_grid(N);
+  const int tiles = 2 * LOB_PAIRS * ((m + LOB_GT - 1) / LOB_GT);
+  if (!dispatch_r(m, [&](auto Mc) {
+        hipLaunchKernelGGL((k_lob_gram<Mc>), dim3(grid, tiles),
+                           dim3(CERT_BS), 0, s, lc, B, SB, gpart, N);
+      }))
+    lob_bad_block(m);
+  hipLaunchKernelGGL(k_lob_gram_finish, dim3(tiles * m * LOB_GT + m),
+                     dim3(CERT_BS), 0, s, lc, (const double*)gpart, rpart,
+                     grid, m, out);
+}
+
+extern "C" {
+
+int dpo_cert_lobpcg_ctrl_size() { return LB_SIZE; }
+// doubles of the partial-slot workspace: Gram slots, then residual slots
+int dpo_cert_lobpcg_part_size() { return LOB_GPART + LOB_RPART; }
+
+// R = SX - X diag(theta); residual partials into part's residual slots.
+// zero may be null.
+void dpo_cert_lobpcg_resid(const double* lc, const double* X,
+                           const double* SX, double* R, double* zero,
+                           double* part, long N, int m, void* stream) {
+  launch_lob_resid(lc, X, SX, R, zero, part + LOB_GPART, N, m,
+                   (hipStream_t)stream);
+}
+
+// SW = (Q - Lambda) W for one (N, m) block
+void dpo_cert_lobpcg_apply(const double* lc, const int* row_ptr,
+                           const int* col_idx, const double* vals,
+                           const double* lam, const double* W, double* SW,
+                           int n, int d, int m, void* stream) {
+  launch_lob_apply(lc, row_ptr, col_idx, vals, lam, W, SW, n, d, m,
+                   (hipStream_t)stream);
+}
+
+// out = [G_B, G_A, residual norms^2] from B, SB (3 blocks each) and the
+// residual slots k_lob_resid left in part
+void dpo_cert_lobpcg_gram(const double* lc, const double* B,
+                          const double* SB, double* part, double* out,
+                          long N, int m, void* stream) {
+  launch_lob_gram(lc, B, SB, part, part + LOB_GPART, out, N, m,
+                  (hipStream_t)stream);
+}
+
+void dpo_cert_lobpcg_update(const double* lc, double* B, double* SB, long N,
+                            int m, void* stream) {
+  if (!dispatch_r(m, [&](auto Mc) {
+        hipLaunchKernelGGL((k_lob_update<Mc>), dim3(cert_grid(N)),
+                           dim3(CERT_BS), 0, (hipStream_t)stream, lc, B, SB,
+                           N);
+      }))
+    lob_bad_block(m);
+}
+
+// The device half of one iteration: residual, W = T R with exactly one
+// of L (block-Jacobi factors) and Minv (dense fp32 inverse), SW = S W,
+// both Gram matrices. Nothing synchronises.
+void dpo_cert_lobpcg_iter(const double* lc, const int* row_ptr,
+                          const int* col_idx, const double* vals,
+                          const double* lam, double* B, double* SB,
+                          double* R, const double* L, const float* Minv,
+                          double* part, double* out, int n, int d, int m,
+                          void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long N = (long)n * (d + 1);
+  double* W = B + (size_t)N * m;
+  double* SW = SB + (size_t)N * m;
+  launch_lob_resid(lc, B, SB, R, Minv != nullptr ? W : nullptr,
+                   part + LOB_GPART, N, m, s);
+  if (Minv != nullptr)  // W was cleared by k_lob_resid
+    launch_precond_dense(Minv, R, W, (int)N, m, lc, 0, s,
+                         /*prezeroed=*/true);
+  else
+    launch_precond_jacobi(L, R, W, n, d + 1, m, lc, 0, s);
+  launch_lob_apply(lc, row_ptr, col_idx, vals, lam, W, SW, n, d, m, s);
+  launch_lob_gram(lc, B, SB, part, part + LOB_GPART, out, N, m, s);
+}
+
+}  // extern "C"

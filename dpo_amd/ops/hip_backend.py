@@ -1008,3 +1008,111 @@ def round_cost(Q, X: Tensor, G: Optional[Tensor] = None) -> Tensor:
     if G is not None:
         dots(X, G.contiguous(), None, acc, C_DOT1)
     return (0.5 * acc[C_DOT0] + acc[C_DOT1]).reshape(1)
+
+
+# ---------------------------------------------------------------------
+# Certificate, LOBPCG (docs/DESIGN.md §20) — interface mirrors
+# cpu_ref.cert_lob_*. Nothing here synchronises with the host.
+# ---------------------------------------------------------------------
+_lib.dpo_cert_lobpcg_ctrl_size.restype = _i
+_lib.dpo_cert_lobpcg_part_size.restype = _i
+_lib.dpo_cert_lobpcg_resid.argtypes = [_c, _c, _c, _c, _c, _c, _l, _i, _c]
+_lib.dpo_cert_lobpcg_apply.argtypes = [_c, _c, _c, _c, _c, _c, _c, _i, _i,
+                                       _i, _c]
+_lib.dpo_cert_lobpcg_gram.argtypes = [_c, _c, _c, _c, _c, _l, _i, _c]
+_lib.dpo_cert_lobpcg_update.argtypes = [_c, _c, _c, _l, _i, _c]
+_lib.dpo_cert_lobpcg_iter.argtypes = [_c, _c, _c, _c, _c, _c, _c, _c, _c,
+                                      _c, _c, _c, _i, _i, _i, _c]
+
+from .cpu_ref import (LOB_GPART, LOB_RPART, LOB_SIZE, LOB_W,  # noqa: E402
+                      LobWorkspace)
+
+assert _lib.dpo_cert_lobpcg_ctrl_size() == LOB_SIZE
+assert _lib.dpo_cert_lobpcg_part_size() == LOB_GPART + LOB_RPART
+
+
+def _chk_lob(ws, d: Optional[int] = None) -> None:
+    N, m = ws.N, ws.m
+    _check_shape(d, m)
+    for t in (ws.B, ws.SB, ws.R, ws.ctl, ws.part, ws.out):
+        _chk(t)
+        assert t.device == ws.B.device
+    assert ws.B.shape == (3, N, m) and ws.SB.shape == (3, N, m)
+    assert ws.R.shape == (N, m) and ws.ctl.numel() == LOB_SIZE
+    assert ws.part.numel() == LOB_GPART + LOB_RPART
+    assert ws.out.numel() == 18 * m * m + m
+
+
+def _lob_pre(ws, pre, d: int):
+    """(L, Minv) pointers' tensors of a (mode, data) preconditioner."""
+    mode, data = pre
+    n = ws.N // (d + 1)
+    if mode == "jacobi":
+        _chk(data)
+        assert data.shape == (n, d + 1, d + 1)
+        return data, None
+    if mode == "dense":
+        _chk(data, torch.float32)
+        assert data.shape == (ws.N, ws.N)
+        return None, data
+    raise ValueError(f"preconditioner mode {mode!r} has no HIP kernel: use "
+                     "'jacobi' or 'dense'")
+
+
+def cert_lob_resid(ws, zero: bool = False) -> None:
+    """R = SX - X diag(theta), per-block partials of the squared column
+    norms in ws.part's residual slots; `zero` clears W."""
+    _chk_lob(ws)
+    _lib.dpo_cert_lobpcg_resid(_p(ws.ctl), _p(ws.B[0]), _p(ws.SB[0]),
+                               _p(ws.R), _p(ws.B[LOB_W]) if zero else None,
+                               _p(ws.part), ws.N, ws.m, _stream(ws.B))
+
+
+def cert_lob_precond(ws, pre, d: int) -> None:
+    """W = T R with the guarded solve kernels (stand-alone: the dense
+    apply clears W by a launch of its own; cert_lob_iter does not)."""
+    _chk_lob(ws, d)
+    L, Minv = _lob_pre(ws, pre, d)
+    if Minv is not None:
+        precond_dense(Minv, ws.R, ws.B[LOB_W], ws.ctl, 0)
+    else:
+        precond_jacobi(L, ws.R, d + 1, ws.B[LOB_W], ws.ctl, 0)
+
+
+def cert_lob_apply(Q, lam: Tensor, ws, blk: int) -> None:
+    """SB[blk] = (Q - Lambda) B[blk]."""
+    n, d = lam.shape[0], lam.shape[1]
+    _chk_lob(ws, d); _chk(lam); _chk_q(Q, ws.B)
+    assert Q.n == n and Q.dh == d + 1 and ws.N == n * (d + 1)
+    assert 0 <= blk < 3
+    _lib.dpo_cert_lobpcg_apply(_p(ws.ctl), _p(Q.row_ptr), _p(Q.col_idx),
+                               _p(Q.vals), _p(lam), _p(ws.B[blk]),
+                               _p(ws.SB[blk]), n, d, ws.m, _stream(ws.B))
+
+
+def cert_lob_gram(ws) -> None:
+    """ws.out = [G_B, G_A (upper block triangles), squared residual
+    norms]; bitwise run-to-run reproducible."""
+    _chk_lob(ws)
+    _lib.dpo_cert_lobpcg_gram(_p(ws.ctl), _p(ws.B), _p(ws.SB), _p(ws.part),
+                              _p(ws.out), ws.N, ws.m, _stream(ws.B))
+
+
+def cert_lob_update(ws) -> None:
+    """X, P, SX, SP from the coefficients in ws.ctl, in place."""
+    _chk_lob(ws)
+    _lib.dpo_cert_lobpcg_update(_p(ws.ctl), _p(ws.B), _p(ws.SB), ws.N, ws.m,
+                                _stream(ws.B))
+
+
+def cert_lob_iter(Q, lam: Tensor, ws, pre) -> None:
+    """Residual, W = T R, SW = S W and both Gram matrices, enqueued with
+    no host synchronisation."""
+    n, d = lam.shape[0], lam.shape[1]
+    _chk_lob(ws, d); _chk(lam); _chk_q(Q, ws.B)
+    assert Q.n == n and Q.dh == d + 1 and ws.N == n * (d + 1)
+    L, Minv = _lob_pre(ws, pre, d)
+    _lib.dpo_cert_lobpcg_iter(_p(ws.ctl), _p(Q.row_ptr), _p(Q.col_idx),
+                              _p(Q.vals), _p(lam), _p(ws.B), _p(ws.SB),
+                              _p(ws.R), _p(L), _p(Minv), _p(ws.part),
+                              _p(ws.out), n, d, ws.m, _stream(ws.B))

@@ -241,7 +241,9 @@ def certified_solve(measurements, n: int, d: int, Xt: Tensor, *,
     repeat. Stops on any other verdict, or with NOT_OPTIMAL when r + 1 is
     outside the compiled shapes or above `max_rank`. Q is assembled once;
     `refine_kw` / `certify_kw` go to `refine_to_critical` /
-    `certify_solution`. With `round=True` the final level's iterate is
+    `certify_solution`; with `certify_kw["method"] == "lobpcg"` the
+    preconditioner of Q is built once and handed to both (`precond=` and
+    `problem=`). With `round=True` the final level's iterate is
     rounded to SE(d) on its device (`rounding.round_solution`,
     mode="svd") and the result carries it as `rounding`: the trajectory,
     its cost and the suboptimality gap, which bounds the distance to the
@@ -258,6 +260,14 @@ def certified_solve(measurements, n: int, d: int, Xt: Tensor, *,
     if Xt.device.type != "cpu":
         Q = Q.to(Xt.device)
     X = Xt.to(torch.float64).contiguous()
+    if (certify_kw.get("method") == "lobpcg"
+            and certify_kw.get("problem") is None):
+        # one preconditioner of Q (it does not depend on the rank) for
+        # the refinement and the LOBPCG certificate of every level
+        pre = refine_kw.get("precond", "auto")
+        if not isinstance(pre, tuple):
+            pre = _preconditioner(Q, n, d, X.shape[1], pre)
+        refine_kw["precond"] = certify_kw["problem"] = pre
     levels: List[StaircaseLevel] = []
     while True:
         r = X.shape[1]

@@ -29,6 +29,13 @@ def build_parser():
                          "of B vectors (basis memory N (B + 1) doubles)")
     ap.add_argument("--cert-max-iters", type=int, default=None, metavar="M",
                     help="with --certify: Lanczos step budget (default 512)")
+    ap.add_argument("--cert-method", default=None,
+                    choices=["lanczos", "lobpcg"],
+                    help="with --certify or --refine: the certificate's "
+                         "eigensolver (default lanczos)")
+    ap.add_argument("--cert-block", type=int, default=None, metavar="M",
+                    help="with --cert-method lobpcg: block size (default "
+                         "rank + 1)")
     ap.add_argument("--refine", action="store_true",
                     help="certified solve: refine the result to criticality "
                          "on the device, certify, and climb the rank "
@@ -105,6 +112,10 @@ def main():
             kw["basis_size"] = args.cert_basis
         if args.cert_max_iters is not None:
             kw["max_iters"] = args.cert_max_iters
+        if args.cert_method is not None:
+            kw["method"] = args.cert_method
+        if args.cert_block is not None:
+            kw["block_size"] = args.cert_block
         if args.refine:
             from dpo_amd.refine import certified_solve
             t_cert = time.perf_counter()
