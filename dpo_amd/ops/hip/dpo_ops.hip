@@ -972,7 +972,7 @@ __device__ __forceinline__ void hess_fused_body(
             d0 = fma(acc[c][k], w, d0);
           }
       }
-      // the next j-split dense apply accumulates into this buffer
+      // clears the buffer in front of the next dense apply
       if (AUX == 1 && zero_out) {
         double* Zi = zero_out + (size_t)i * dh * R;
         #pragma unroll
@@ -1289,82 +1289,164 @@ __global__ void k_polar_affine(const double* __restrict__ A,
 
 // ---------------------------------------------------------------------
 // Dense fp32 preconditioner apply: Z(N, r) = Minv(N, N) @ V(N, r).
-// Minv is symmetric -> read column-major (Minv[j*N+i]) so consecutive
-// threads (i) are coalesced; j-loop broadcasts V[j][*] via LDS.
+// Minv is symmetric -> read as Minv[j*N+i], so the lanes that share a
+// matrix row j read consecutive output rows i (coalesced).
 // fp32 storage halves the bandwidth; accumulate fp64.
 // ---------------------------------------------------------------------
-// Z = Minv @ V with Minv symmetric fp32 read column-wise (coalesced).
-// The j loop is SPLIT across gridDim.y so small problems still fill the
-// chip (MI355X: 256 CUs want >> 256 workgroups); partial sums combine
-// with fp64 atomics into the zeroed output.
-// jsplit is the number of j chunks (the grid's y extent in a single-agent
-// launch, the agent's own split in a batched one).
+// A block owns a strip of DENSE_STRIP output rows, one 128-byte segment
+// of every matrix row, and the whole j range: no sum crosses a block, so
+// Z is written with plain stores in a fixed summation order (no atomics,
+// no zeroed output, bit-reproducible). Eight lanes cover a row's segment
+// with four output rows each; a wave takes 8 matrix rows per load
+// instruction and the 256-thread block DENSE_ROWS = 32. Every lane keeps
+// DENSE_LOADS independent loads in flight before the first is consumed,
+// so V is staged through LDS in tiles of 32 * DENSE_LOADS rows.
+constexpr int DENSE_STRIP = 32;
+constexpr int DENSE_ROWS = 32;
+constexpr int DENSE_LOADS = 8;
+constexpr int DENSE_TILE_J = DENSE_ROWS * DENSE_LOADS;
+
+static inline int precond_dense_strips(int N) {
+  return (N + DENSE_STRIP - 1) / DENSE_STRIP;
+}
+
+// The 16-byte loads need every row segment aligned: N % 4 == 0 and an
+// aligned base (every d = 3 shape). Anything else takes the VEC = false
+// instantiation: 4-byte loads, the same strip, reduction and stores, and
+// therefore the same bits.
+static inline bool precond_dense_vec_ok(const float* Minv, int N) {
+  return N % 4 == 0 && ((uintptr_t)Minv & 15) == 0;
+}
+
+// One lane's loads of a tile of DENSE_TILE_J matrix rows from j0: its
+// DENSE_LOADS pieces of four matrix entries and its R elements of the V
+// tile. Branch-free and unmasked, so every load is in flight and nothing
+// waits here: addresses are clamped into the arrays (a row at or beyond N
+// re-reads the last one), and the consumer zeroes the V tile's rows at or
+// beyond N instead.
 template <int R>
-__device__ __forceinline__ void precond_dense_body(
-    const float* __restrict__ Minv, const double* __restrict__ V,
-    double* __restrict__ Z, int N, const double* __restrict__ ctrl,
-    int guard, int jsplit) {
-  if (guarded_off(ctrl, guard)) return;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  const int jchunk = (N + jsplit - 1) / jsplit;
-  const int j_lo = blockIdx.y * jchunk;
-  const int j_hi = min(N, j_lo + jchunk);
-  constexpr int TILE_J = 64;
-  __shared__ double shv[TILE_J * R];
-  double acc[R];
+struct DenseTile {
+  float m[DENSE_LOADS][4];
+  double v[R];
+};
+
+template <int R, bool VEC>
+__device__ __forceinline__ void dense_tile_load(
+    DenseTile<R>& t, const float* __restrict__ Minv,
+    const double* __restrict__ V, int N, int j0, int i) {
+  const int tid = threadIdx.x;
+  const int g = tid >> 3;
   #pragma unroll
-  for (int k = 0; k < R; ++k) acc[k] = 0.0;
-  for (int j0 = j_lo; j0 < j_hi; j0 += TILE_J) {
-    const int jn = min(TILE_J, j_hi - j0);
-    __syncthreads();
-    for (int t = threadIdx.x; t < jn * R; t += blockDim.x)
-      shv[t] = V[(size_t)(j0 + t / R) * R + (t % R)];
-    __syncthreads();
-    if (i < N) {
-      // eight independent 4-byte loads in flight per lane before the
-      // first is consumed (one dependent load per j left the kernel at
-      // ~0.55 TB/s); the fma order over j is unchanged
-      const float* Mc = Minv + (size_t)j0 * N + i;
-      int j = 0;
-      for (; j + 8 <= jn; j += 8) {
-        float m[8];
-        #pragma unroll
-        for (int u = 0; u < 8; ++u) m[u] = Mc[(size_t)(j + u) * N];
-        #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const double md = (double)m[u];
-          #pragma unroll
-          for (int k = 0; k < R; ++k)
-            acc[k] = fma(md, shv[(j + u) * R + k], acc[k]);
-        }
-      }
-      for (; j < jn; ++j) {
-        const double md = (double)Mc[(size_t)j * N];
-        #pragma unroll
-        for (int k = 0; k < R; ++k)
-          acc[k] = fma(md, shv[j * R + k], acc[k]);
-      }
-    }
-  }
-  if (i < N) {
-    if (jsplit == 1) {
-      #pragma unroll
-      for (int k = 0; k < R; ++k) Z[(size_t)i * R + k] = acc[k];
+  for (int u = 0; u < DENSE_LOADS; ++u) {
+    const int j = j0 + g + DENSE_ROWS * u;
+    const float* Mj = Minv + (size_t)min(j, N - 1) * N;
+    if (VEC) {
+      const float4 f = *reinterpret_cast<const float4*>(Mj + (i < N ? i : 0));
+      t.m[u][0] = f.x; t.m[u][1] = f.y; t.m[u][2] = f.z; t.m[u][3] = f.w;
     } else {
       #pragma unroll
-      for (int k = 0; k < R; ++k)
-        atomicAdd(&Z[(size_t)i * R + k], acc[k]);
+      for (int v = 0; v < 4; ++v) t.m[u][v] = Mj[min(i + v, N - 1)];
     }
+  }
+  const long total = (long)N * R;
+  #pragma unroll
+  for (int c = 0; c < R; ++c) {
+    const long e = (long)j0 * R + tid + 256 * c;
+    t.v[c] = V[e < total ? e : total - 1];
   }
 }
 
-template <int R>
-__global__ void k_precond_dense(const float* __restrict__ Minv,
-                                const double* __restrict__ V,
-                                double* __restrict__ Z,
-                                int N, const double* __restrict__ ctrl,
-                                int guard) {
-  precond_dense_body<R>(Minv, V, Z, N, ctrl, guard, (int)gridDim.y);
+// Element `threadIdx.x` of the strip's DENSE_STRIP x R block of Z (row-
+// major, contiguous in Z), valid in threads < DENSE_STRIP * R; sh holds
+// DENSE_TILE_J * R doubles. Rows at or beyond N come out as zero. Every
+// thread of the 256-thread block must call it (barriers inside).
+template <int R, bool VEC>
+__device__ __forceinline__ double precond_dense_strip_sum(
+    const float* __restrict__ Minv, const double* __restrict__ V, int N,
+    int strip, double* sh) {
+  static_assert(DENSE_STRIP * R <= 256 && 4 * DENSE_STRIP <= DENSE_TILE_J,
+                "strip tile must fit the block and the V tile");
+  const int tid = threadIdx.x;
+  const int q = tid & 7;   // which 4 output rows of the strip
+  const int g = tid >> 3;  // which matrix row of a pass of DENSE_ROWS
+  const int i = strip * DENSE_STRIP + 4 * q;
+  double acc[4][R];
+  #pragma unroll
+  for (int v = 0; v < 4; ++v)
+    #pragma unroll
+    for (int k = 0; k < R; ++k) acc[v][k] = 0.0;
+  // The next tile's loads are issued behind the barriers and in front of
+  // the current tile's arithmetic, which hides their round trip; the
+  // scheduling barrier keeps the compiler from sinking them below it.
+  const long total = (long)N * R;
+  DenseTile<R> nxt;
+  dense_tile_load<R, VEC>(nxt, Minv, V, N, 0, i);
+  for (int j0 = 0; j0 < N; j0 += DENSE_TILE_J) {
+    const DenseTile<R> cur = nxt;
+    __syncthreads();
+    #pragma unroll
+    for (int c = 0; c < R; ++c)
+      sh[tid + 256 * c] =
+          (long)j0 * R + tid + 256 * c < total ? cur.v[c] : 0.0;
+    __syncthreads();
+    dense_tile_load<R, VEC>(nxt, Minv, V, N, j0 + DENSE_TILE_J, i);
+    __builtin_amdgcn_sched_barrier(0);
+    #pragma unroll
+    for (int u = 0; u < DENSE_LOADS; ++u)
+      #pragma unroll
+      for (int k = 0; k < R; ++k) {
+        const double vk = sh[(g + DENSE_ROWS * u) * R + k];
+        #pragma unroll
+        for (int v = 0; v < 4; ++v)
+          acc[v][k] = fma((double)cur.m[u][v], vk, acc[v][k]);
+      }
+  }
+  // the wave's 8 row groups in a fixed butterfly order, then the 4 waves
+  // through LDS in a fixed order
+  #pragma unroll
+  for (int v = 0; v < 4; ++v)
+    #pragma unroll
+    for (int k = 0; k < R; ++k) {
+      double s = acc[v][k];
+      s += __shfl_xor(s, 8);
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      acc[v][k] = s;
+    }
+  __syncthreads();
+  if ((tid & 63) < 8) {
+    double* dst = sh + ((tid >> 6) * DENSE_STRIP + 4 * q) * R;
+    #pragma unroll
+    for (int v = 0; v < 4; ++v)
+      #pragma unroll
+      for (int k = 0; k < R; ++k) dst[v * R + k] = acc[v][k];
+  }
+  __syncthreads();
+  constexpr int SR = DENSE_STRIP * R;
+  double zt = 0.0;
+  if (tid < SR)
+    zt = ((sh[tid] + sh[SR + tid]) + sh[2 * SR + tid]) + sh[3 * SR + tid];
+  return zt;
+}
+
+template <int R, bool VEC>
+__device__ __forceinline__ void precond_dense_body(
+    const float* __restrict__ Minv, const double* __restrict__ V,
+    double* __restrict__ Z, int N, const double* __restrict__ ctrl,
+    int guard, int strip) {
+  if (guarded_off(ctrl, guard)) return;
+  __shared__ double sh[DENSE_TILE_J * R];
+  const double zt = precond_dense_strip_sum<R, VEC>(Minv, V, N, strip, sh);
+  const long e = (long)strip * DENSE_STRIP * R + threadIdx.x;
+  if ((int)threadIdx.x < DENSE_STRIP * R && e < (long)N * R) Z[e] = zt;
+}
+
+template <int R, bool VEC>
+__global__ void __launch_bounds__(256)
+k_precond_dense(const float* __restrict__ Minv, const double* __restrict__ V,
+                double* __restrict__ Z, int N,
+                const double* __restrict__ ctrl, int guard) {
+  precond_dense_body<R, VEC>(Minv, V, Z, N, ctrl, guard, (int)blockIdx.x);
 }
 
 // Block-Jacobi apply: per pose solve (L L^T) z = v with stored Cholesky
@@ -1425,9 +1507,8 @@ __device__ __forceinline__ void tcg_update_body(
       __builtin_nontemporal_store(et, &eta_snap[(size_t)j * total + i]);
       __builtin_nontemporal_store(dl, &delta_snap[(size_t)j * total + i]);
       eta[i] = fma(coef, dl, et);
-      // z is dead until the next j-split dense apply accumulates into
-      // it: clear it here instead of in a launch of its own (nullptr
-      // on the Jacobi path, which overwrites z)
+      // z is dead until the next dense apply writes it: clear it here
+      // instead of in a launch of its own (nullptr on the Jacobi path)
       if (zero_out) zero_out[i] = 0.0;
       if (!stop_pending) {
         const double rn = fma(coef, Hd[i], rvec[i]);
@@ -1907,29 +1988,20 @@ static inline void dzero(double* p, long n, hipStream_t s) {
                      n);
 }
 
-// j-split so small problems still produce >= ~512 workgroups
-static inline int precond_dense_jsplit(int N) {
-  const int gx = blocks_for(N, 256);
-  int jsplit = 1;
-  while (gx * jsplit < 512 && jsplit < 32) jsplit *= 2;
-  return jsplit;
-}
-
-// prezeroed: the caller guarantees Z is already all-zero wherever the
-// j-split partial sums accumulate (the solve body folds that zeroing
-// into the kernel that runs just before).
+// Overwrites every element of Z unless guarded off (then Z is untouched).
 static void launch_precond_dense(const float* Minv, const double* V,
                                  double* Z, int N, int r,
                                  const double* ctrl, int guard,
-                                 hipStream_t s, bool prezeroed = false) {
-  const int gx = blocks_for(N, 256);
-  const int jsplit = precond_dense_jsplit(N);
-  // kernel (not hipMemsetAsync): this runs inside captured graphs,
-  // which must stay free of SDMA nodes (see fence comment)
-  if (jsplit > 1 && !prezeroed) dzero(Z, (long)N * r, s);
+                                 hipStream_t s) {
+  const int strips = precond_dense_strips(N);
+  const bool vec = precond_dense_vec_ok(Minv, N);
   if (!dispatch_r(r, [&](auto Rc) {
-        hipLaunchKernelGGL((k_precond_dense<Rc>), dim3(gx, jsplit),
-                           dim3(256), 0, s, Minv, V, Z, N, ctrl, guard);
+        if (vec)
+          hipLaunchKernelGGL((k_precond_dense<Rc, true>), dim3(strips),
+                             dim3(256), 0, s, Minv, V, Z, N, ctrl, guard);
+        else
+          hipLaunchKernelGGL((k_precond_dense<Rc, false>), dim3(strips),
+                             dim3(256), 0, s, Minv, V, Z, N, ctrl, guard);
       }))
     dpo_bad_shape(-1, r);
 }
@@ -2002,6 +2074,10 @@ void dpo_polar_affine(const double* A, const double* B, const double* C,
 void dpo_precond_dense(const float* Minv, const double* V, double* Z,
                        int N, int r, const double* ctrl, int guard,
                        void* stream) {
+  // stand-alone entry: Z is exactly zero when the launch is guarded off.
+  // Kernel (not hipMemsetAsync): callers may capture this into graphs,
+  // which must stay free of SDMA nodes (see fence comment)
+  dzero(Z, (long)N * r, (hipStream_t)stream);
   launch_precond_dense(Minv, V, Z, N, r, ctrl, guard, (hipStream_t)stream);
 }
 
@@ -2351,21 +2427,18 @@ static void ctx_assemble_g(DpoCtx* c, const double* nbr, hipStream_t s,
                      c->g_nbr_slot, nbr, c->g_w, c->g_ne, c->dh, c->r);
 }
 
-// The buffer the solve body must have cleared before each dense apply:
-// z when the apply is j-split (its partial sums accumulate), nullptr on
-// the Jacobi path and for an unsplit apply, which overwrite z.
+// The buffer the solve body clears in front of each dense apply: z on the
+// dense path, nullptr on the Jacobi path. The strip apply overwrites z
+// and no longer needs it; the clearing stays until its tests move.
 static inline double* ctx_prezero_z(const DpoCtx* c) {
-  return (c->Minv && precond_dense_jsplit(c->N) > 1) ? c->z : nullptr;
+  return c->Minv ? c->z : nullptr;
 }
 
-// Solve-body preconditioner apply into c->z. The dense apply relies on
-// the kernel in front of it (gradient k_hess_fused for z0, k_tcg_update
-// in the loop) having cleared ctx_prezero_z(c).
+// Solve-body preconditioner apply into c->z.
 static void ctx_precond(DpoCtx* c, const double* V, double* Z,
                         hipStream_t s) {
   if (c->Minv)
-    launch_precond_dense(c->Minv, V, Z, c->N, c->r, c->ctrl, ST_RUN, s,
-                         /*prezeroed=*/true);
+    launch_precond_dense(c->Minv, V, Z, c->N, c->r, c->ctrl, ST_RUN, s);
   else
     launch_precond_jacobi(c->Ljac, V, Z, c->n, c->dh, c->r, c->ctrl,
                           ST_RUN, s);
@@ -3223,8 +3296,8 @@ struct BatchDesc {
 static void batch_desc_extents(BatchDesc& b, int dh, int r) {
   b.nb_pose = blocks_for(b.n, 256);
   b.nb_upd = blocks_for((b.total + 3) / 4, 256);
-  b.nb_dense = blocks_for(b.N, 256);
-  b.jsplit = precond_dense_jsplit(b.N);
+  b.nb_dense = precond_dense_strips(b.N);
+  b.jsplit = 1;  // the strip apply does not split j
   b.nb_gasm = blocks_for((long)b.g_ne * dh * r, 256);
   b.nb_zero = blocks_for(b.gtotal, 256);
   b.nb_zero2 = blocks_for(b.gtotal > CTRL_SIZE ? b.gtotal : (long)CTRL_SIZE,
@@ -3289,12 +3362,15 @@ __global__ void kb_hess(const BatchDesc* __restrict__ desc, TailArgs ta) {
   }
 }
 
-// z = Minv rvec; grid (max blocks, max j-split, agents)
-template <int R>
-__global__ void kb_precond_dense(const BatchDesc* __restrict__ desc) {
-  const BatchDesc& a = desc[blockIdx.z];
-  if ((int)blockIdx.x >= a.nb_dense || (int)blockIdx.y >= a.jsplit) return;
-  precond_dense_body<R>(a.Minv, a.rvec, a.z, a.N, a.ctrl, ST_RUN, a.jsplit);
+// z = Minv rvec; grid (max strips, agents). VEC only when every agent of
+// the batch is eligible (BatchExtents::vec); the bits do not depend on it.
+template <int R, bool VEC>
+__global__ void __launch_bounds__(256)
+kb_precond_dense(const BatchDesc* __restrict__ desc) {
+  const BatchDesc& a = desc[blockIdx.y];
+  if ((int)blockIdx.x >= a.nb_dense) return;
+  precond_dense_body<R, VEC>(a.Minv, a.rvec, a.z, a.N, a.ctrl, ST_RUN,
+                             (int)blockIdx.x);
 }
 
 // z = P_X(z), <z, rvec>, tail CF_Z0 / CF_BETA
@@ -3354,14 +3430,15 @@ __global__ void k_fence_wait_many(unsigned int* const* __restrict__ f,
 
 // Grid extents of a batch: the maximum of every per-agent extent.
 struct BatchExtents {
-  int k = 0, pose = 1, upd = 1, dense = 1, js = 1, gasm = 0, zero = 0,
-      zero2 = 1, copy = 1;
+  int k = 0, pose = 1, upd = 1, dense = 1, gasm = 0, zero = 0, zero2 = 1,
+      copy = 1;
+  bool vec = true;  // every agent passes precond_dense_vec_ok
   void add(const BatchDesc& b) {
     ++k;
     pose = b.nb_pose > pose ? b.nb_pose : pose;
     upd = b.nb_upd > upd ? b.nb_upd : upd;
     dense = b.nb_dense > dense ? b.nb_dense : dense;
-    js = b.jsplit > js ? b.jsplit : js;
+    vec = vec && precond_dense_vec_ok(b.Minv, b.N);
     gasm = b.nb_gasm > gasm ? b.nb_gasm : gasm;
     zero = b.nb_zero > zero ? b.nb_zero : zero;
     zero2 = b.nb_zero2 > zero2 ? b.nb_zero2 : zero2;
@@ -3383,8 +3460,12 @@ static void launch_kb_hess(const BatchDesc* dd, const BatchExtents& e, int d,
 static void launch_kb_precond(const BatchDesc* dd, const BatchExtents& e,
                               int r, hipStream_t s) {
   if (!dispatch_r(r, [&](auto Rc) {
-        hipLaunchKernelGGL((kb_precond_dense<Rc>), dim3(e.dense, e.js, e.k),
-                           dim3(256), 0, s, dd);
+        if (e.vec)
+          hipLaunchKernelGGL((kb_precond_dense<Rc, true>),
+                             dim3(e.dense, e.k), dim3(256), 0, s, dd);
+        else
+          hipLaunchKernelGGL((kb_precond_dense<Rc, false>),
+                             dim3(e.dense, e.k), dim3(256), 0, s, dd);
       }))
     dpo_bad_shape(-1, r);
 }
@@ -4684,8 +4765,8 @@ __global__ void k_ref_ctl(double* __restrict__ rc,
 //   RP_Z     in = M^-1 r from the dense apply: z = P_X(T) in place;
 //            part0 += <z, r>
 //   RP_ZJ    T = block-Jacobi solve of r with the factors L; then RP_Z
-// zero, when given, has this pose's tile cleared (the j-split dense
-// apply that follows accumulates into it).
+// zero, when given, has this pose's tile cleared in front of the dense
+// apply that follows.
 enum RefProj { RP_GRAD = 0, RP_HD = 1, RP_Z = 2, RP_ZJ = 3 };
 
 // Launched with CERT_BS threads only: the bound lets the wide shapes keep
@@ -4854,7 +4935,7 @@ static void ref_precond(const RefBufs& b, hipStream_t s) {
   if (b.Minv != nullptr) {
     // z was cleared by the kernel that wrote r
     launch_precond_dense(b.Minv, b.rvec, b.z, b.n * (b.d + 1), b.r, b.rc,
-                         RS_RUN, s, /*prezeroed=*/true);
+                         RS_RUN, s);
     ref_proj<RP_Z>(b, RS_RUN, b.z, b.rvec, b.z, nullptr, nullptr, nullptr,
                    s);
   } else {
@@ -5372,7 +5453,7 @@ __device__ __forceinline__ bool lob_off(const double* lc) {
 
 // R = SX - X diag(theta), one thread per row; rpart[j * grid + block] =
 // block partial of ||R[:, j]||^2. zero != nullptr: that (N, m) block is
-// cleared (the j-split partial sums of k_precond_dense accumulate there).
+// cleared in front of k_precond_dense.
 template <int M>
 __global__ void __launch_bounds__(CERT_BS)
 k_lob_resid(const double* __restrict__ lc, const double* __restrict__ X,
@@ -5685,8 +5766,7 @@ void dpo_cert_lobpcg_iter(const double* lc, const int* row_ptr,
   launch_lob_resid(lc, B, SB, R, Minv != nullptr ? W : nullptr,
                    part + LOB_GPART, N, m, s);
   if (Minv != nullptr)  // W was cleared by k_lob_resid
-    launch_precond_dense(Minv, R, W, (int)N, m, lc, 0, s,
-                         /*prezeroed=*/true);
+    launch_precond_dense(Minv, R, W, (int)N, m, lc, 0, s);
   else
     launch_precond_jacobi(L, R, W, n, d + 1, m, lc, 0, s);
   launch_lob_apply(lc, row_ptr, col_idx, vals, lam, W, SW, n, d, m, s);
