@@ -20,7 +20,9 @@ None of these is fitted to what the kernels return.
 """
 from __future__ import annotations
 
+import functools
 import math
+from types import SimpleNamespace
 from typing import Optional
 
 import numpy as np
@@ -1063,3 +1065,257 @@ def nbr_from_dict(agent) -> Tensor:
     return torch.from_numpy(np.stack(
         [agent.neighbor_pose_dict[pid].T
          for pid in agent._nbr_slot_order]))
+
+
+# ---------------------------------------------------------------------
+# certificate kernel matrix (tests/test_cert_kernel_matrix.py): the six
+# Lanczos-path kernels k_cert_lambda, k_cert_apply, k_cert_gram,
+# k_cert_sub, k_cert_norm, k_cert_reduce
+# ---------------------------------------------------------------------
+CERT_M = 8                      # basis size of the dissected step
+CERT_STEPS = (0, 1, 5)
+CERT_PAD = 64                   # sentinel slots on either side of a buffer
+CERT_SENTINEL = -7.25e77
+CERT_BETA_PREV = 0.37
+# one pose past 256 blocks x 256 threads, at the two largest register tiles
+CERT_LAMBDA_WRAP = {(2, 6): 65537, (3, 8): 65537}
+# thread-per-row kernels, N = (d + 1) n: 3 / 192 / 195 and 65 538 (two
+# rows on a second grid-stride trip) for d = 2; 4 / 256 / 260, 65 536
+# (256 full blocks, no second trip) and 65 540 (four rows on one) for d = 3
+CERT_ROW_POSES = {2: (1, 64, 65, 21846), 3: (1, 64, 65, 16384, 16385)}
+
+
+def cert_lambda_poses(d: int, r: int):
+    wrap = CERT_LAMBDA_WRAP.get((d, r))
+    return N_POSE + ((wrap,) if wrap else ())
+
+
+def cert_steps_for(N: int):
+    """Step j needs j + 1 orthonormal basis rows and a direction left for
+    v_{j+1}: j + 2 <= N (N = 3 and 4 cannot hold step 5)."""
+    return tuple(j for j in CERT_STEPS if j + 2 <= N)
+
+
+@functools.lru_cache(maxsize=None)
+def cert_matrix(n: int, d: int):
+    """(Q, |Q|) of random_bsr(n, d + 1), built once per (n, d) with the
+    scalar-CSR mirrors the CPU reference multiplies with."""
+    Q = random_bsr(n, d + 1, gen(40, n, d))
+    Qa = BSRMatrix(Q.n, Q.dh, Q.row_ptr, Q.col_idx, Q.vals.abs())
+    Q.to_scalar_csr()
+    Qa.to_scalar_csr()
+    return Q, Qa
+
+
+def cert_zero_matrix(n: int, d: int):
+    """The pattern of cert_matrix(n, d) with every stored value zero."""
+    Q, _ = cert_matrix(n, d)
+    return BSRMatrix(Q.n, Q.dh, Q.row_ptr, Q.col_idx,
+                     torch.zeros_like(Q.vals))
+
+
+def cert_lam_blocks(n: int, d: int, g: torch.Generator) -> Tensor:
+    """Random symmetric (n, d, d) blocks, independent of Q."""
+    A = randn(g, n, d, d)
+    return (0.5 * (A + A.transpose(1, 2))).contiguous()
+
+
+def cert_basis(N: int, j: int, m: int, g: torch.Generator) -> Tensor:
+    """(m + 1, N) basis: rows 0..j are the Q factor of a random
+    N x (j + 1) matrix, every later row is CERT_SENTINEL."""
+    assert j + 1 <= N
+    V = torch.full((m + 1, N), CERT_SENTINEL, dtype=torch.float64)
+    V[:j + 1] = torch.linalg.qr(randn(g, N, j + 1))[0].T
+    return V
+
+
+def cert_ctl(m: int, j: int, tol: float = 0.0,
+             beta_prev: float = CERT_BETA_PREV) -> Tensor:
+    """Control array with a distinct finite marker in every slot but the
+    flag (0), the threshold and beta_{j-1}."""
+    ctl = 100.0 + 0.375 * torch.arange(cpu_ref.CERT_HDR + 2 * m,
+                                       dtype=torch.float64)
+    ctl[cpu_ref.CERT_FLAG] = 0.0
+    ctl[cpu_ref.CERT_TOL] = tol
+    if j > 0:
+        ctl[cpu_ref.CERT_HDR + m + j - 1] = beta_prev
+    return ctl
+
+
+def cert_step_state(n: int, d: int, j: int, m: int = CERT_M,
+                    tol: float = 0.0, beta_prev: float = CERT_BETA_PREV):
+    """(Q, |Q|, lam, V, ctl) of one Lanczos step j at (n, d)."""
+    g = gen(43, n, d, j)
+    Q, Qa = cert_matrix(n, d)
+    lam = cert_lam_blocks(n, d, g)
+    V = cert_basis(n * (d + 1), j, m, g)
+    return Q, Qa, lam, V, cert_ctl(m, j, tol, beta_prev)
+
+
+# ---- k_cert_lambda ---------------------------------------------------
+def cert_lambda_ref(X: Tensor, QX: Tensor, d: int):
+    """Lambda_i = sym(QX_i Y_i^T) and res = ||QX - Lambda X||_F^2 from X and
+    a given QX (the arithmetic of cpu_ref.cert_lambda without its sparse
+    product), with their bounds.
+
+    lam: each entry is half a sum of 2 r products plus the halving:
+    sop_bound(sym(|QX||Y|^T), 2 r + 1). g = QX - Lambda Y on the rotation
+    rows: the lam error enters through |Y|, and the d products subtracted
+    from QX add sop_bound(|QX| + |Lambda||Y|, d + 1); translation rows are
+    copies. res = sum g^2 over T = n (d + 1) r non-negative terms:
+    sum (2 |g| b_g + b_g^2) + sop_bound(sum g^2, T).
+    Returns (lam, res, b_lam, b_res)."""
+    r = X.shape[1]
+    Xb, Gb = _pose(X, d), _pose(QX, d)
+    Y, G = Xb[:, :d, :], Gb[:, :d, :]
+    A = torch.bmm(G, Y.transpose(1, 2))
+    lam = 0.5 * (A + A.transpose(1, 2))
+    Aa = torch.bmm(G.abs(), Y.abs().transpose(1, 2))
+    b_lam = sop_bound(0.5 * (Aa + Aa.transpose(1, 2)), 2 * r + 1)
+    g = Gb.clone()
+    g[:, :d, :] -= torch.bmm(lam, Y)
+    b_g = torch.zeros_like(g)
+    b_g[:, :d, :] = torch.bmm(b_lam, Y.abs()) + sop_bound(
+        G.abs() + torch.bmm(lam.abs(), Y.abs()), d + 1)
+    res = float((g * g).sum())
+    b_res = float((2.0 * g.abs() * b_g + b_g * b_g).sum()) + float(
+        sop_bound(res, g.numel()))
+    return lam.contiguous(), res, b_lam, b_res
+
+
+def _pose(X: Tensor, d: int) -> Tensor:
+    return X.view(-1, d + 1, X.shape[1])
+
+
+# ---- k_cert_apply ----------------------------------------------------
+def cert_apply_terms(Q: BSRMatrix, d: int) -> int:
+    """Most products accumulated into one entry of w: the longest BSR
+    row, the d Lambda products and the beta term."""
+    return bsr_max_row_terms(Q) + d + 1
+
+
+def cert_apply_ref(Q: BSRMatrix, Qa: BSRMatrix, lam: Tensor, v: Tensor,
+                   vprev: Optional[Tensor] = None, beta: float = 0.0):
+    """w = (Q - Lambda) v - beta vprev and alpha = <v, w> by
+    cpu_ref.cert_apply, with bounds from the same function on abs()
+    copies: b_w = 2 K eps (|Q||v| + |Lambda||v| + |beta||vprev|) entry-wise,
+    b_alpha = dot_bound(v, w) + sum |v| b_w. Returns (w, alpha, b_w,
+    b_alpha)."""
+    d = lam.shape[1]
+    w, alpha = cpu_ref.cert_apply(Q, lam, v, vprev, beta)
+    w_abs, _ = cpu_ref.cert_apply(
+        Qa, -lam.abs(), v.abs(), None if vprev is None else vprev.abs(),
+        -abs(beta))
+    b_w = sop_bound(w_abs, cert_apply_terms(Q, d))
+    b_alpha = dot_bound(v, w) + float((v.abs() * b_w).sum())
+    return w, float(alpha), b_w, b_alpha
+
+
+# ---- one Lanczos step ------------------------------------------------
+def cert_step_ref(Q: BSRMatrix, Qa: BSRMatrix, lam: Tensor, V: Tensor,
+                  ctl: Tensor, j: int) -> SimpleNamespace:
+    """Step j of cpu_ref.cert_lanczos_steps, operation for operation, with
+    the intermediates the device leaves in w, cvec and part and a bound
+    for each (tests/test_kernel_refs.py shows that these and cpu_ref's own
+    alpha, beta and v_{j+1} lie within half the bound of a longdouble run
+    of the step).
+
+    Derivation, every bound entry-wise and valid for any summation order:
+      apply   b_w = 2 K eps (|Q||v_j| + |Lambda||v_j| + |beta||v_{j-1}|),
+              K = cert_apply_terms; b_alpha = dot_bound + sum |v_j| b_w.
+      CGS pass (twice), B = V[0..j]:
+        c = B w is j + 1 sums of N products of an inexact w:
+              b_c = 2 N eps |B||w| + |B| b_w
+        w' = w - B^T c adds j + 1 products to w, per row:
+              b_w' = b_w + |B|^T b_c + 2 (j + 2) eps (|w| + |B|^T |c|)
+        The second pass's c is about eps ||w||: it is compared under the
+        absolute b_c, never relatively.
+      beta^2 = sum w^2 (what the part slots add up to), N terms:
+              b_beta2 = sum (2 |w| b_w + b_w^2) + 2 N eps sum w^2
+      beta:   | ||w + e|| - ||w|| | <= ||e||_2, and the two norm
+              evaluations round by at most N eps beta between them:
+              b_beta = ||b_w||_2 + N eps beta
+      v_{j+1} = w / beta: |dv| <= (b_w + |w| b_beta / beta) / beta. The
+              roundings of the division (1.5 eps |v| between w / beta and
+              w * (1 / beta)) sit inside the head room of b_w, which is
+              at least (j + 2) eps |w|.
+    """
+    m = V.shape[0] - 1
+    N = V.shape[1]
+    d = lam.shape[1]
+    hdr = cpu_ref.CERT_HDR
+    vj = V[j]
+    w = cpu_ref._cert_s_apply(Q.to_scalar_csr(), lam, vj)
+    w_abs = cpu_ref._cert_s_apply(Qa.to_scalar_csr(), -lam.abs(), vj.abs())
+    if j > 0:
+        w -= ctl[hdr + m + j - 1] * V[j - 1]
+        w_abs += ctl[hdr + m + j - 1].abs() * V[j - 1].abs()
+    out = SimpleNamespace(j=j, N=N)
+    b_w = sop_bound(w_abs, cert_apply_terms(Q, d))
+    out.w0, out.b_w0 = w.clone(), b_w
+    out.alpha = float(torch.dot(vj, w))
+    out.b_alpha = dot_bound(vj, w) + float((vj.abs() * b_w).sum())
+    B = V[:j + 1]
+    Ba = B.abs()
+    for p in (1, 2):
+        c = B @ w
+        b_c = sop_bound(Ba @ w.abs(), N) + Ba @ b_w
+        b_w = b_w + Ba.T @ b_c + sop_bound(w.abs() + Ba.T @ c.abs(), j + 2)
+        w = w - B.T @ c
+        setattr(out, f"c{p}", c)
+        setattr(out, f"b_c{p}", b_c)
+        setattr(out, f"w{p}", w.clone())
+        setattr(out, f"b_w{p}", b_w)
+    out.beta = float(torch.linalg.norm(w))
+    out.beta2 = float((w * w).sum())
+    out.b_beta2 = float((2.0 * w.abs() * b_w + b_w * b_w).sum()) + float(
+        sop_bound(out.beta2, N))
+    out.b_beta = float(torch.linalg.norm(b_w)) + N * EPS * out.beta
+    if out.beta > 0.0:
+        out.vnext = w / out.beta
+        out.b_v = (b_w + w.abs() * (out.b_beta / out.beta)) / out.beta
+    return out
+
+
+# ---- fixed-order fan-in (DESIGN §8) -----------------------------------
+def cert_fixed_order_sum(part, wave_order=(0, 1, 2, 3)) -> float:
+    """cert_sum_partials in NumPy fp64, in the device's order: slot t of
+    <= 256 goes to thread t (the rest add 0.0), each 64-lane wave runs
+    the xor-shuffle tree v += v[lane ^ off] for off = 32, 16, 8, 4, 2, 1,
+    then the four wave sums are added in sequence, wave 0 first.
+    wave_order exists so that the CPU check can show that another order
+    gives another result."""
+    p = np.zeros(256, dtype=np.float64)
+    part = np.asarray(part, dtype=np.float64)
+    assert part.ndim == 1 and part.size <= 256
+    p[:part.size] = part
+    lanes = np.arange(64)
+    sh = []
+    for wv in range(4):
+        v = p[64 * wv:64 * wv + 64].copy()
+        for off in (32, 16, 8, 4, 2, 1):
+            v = v + v[lanes ^ off]
+        assert (v == v[0]).all() or np.isnan(v).any()
+        sh.append(v[0])
+    s = sh[wave_order[0]]
+    for wv in wave_order[1:]:
+        s = s + sh[wv]
+    return float(s)
+
+
+def cert_fanin_cases():
+    """{label: 256 partials} with 1e16, 1, -1e16 in slots 0, 1 and 255.
+    "sparse": zeros elsewhere; there 1e16 + 1 rounds to 1e16 in every
+    order, so it pins the result (0.0, not the exact 1.0) but not the
+    order. "dense": the other slots hold Gaussians scaled over
+    1e-3..1e17. The two 1e16 have the same ulp, and rounding is
+    symmetric, so only values with other ulps make the wave order, a
+    plain left-to-right sum and the exact sum all differ from the device
+    order (tests/test_kernel_refs.py asserts that they do)."""
+    g = gen(44)
+    sparse = np.zeros(256)
+    dense = (randn(g, 256) * 10.0 ** (20.0 * torch.rand(
+        256, dtype=torch.float64, generator=g) - 3.0)).numpy()
+    for p in (sparse, dense):
+        p[0], p[1], p[255] = 1e16, 1.0, -1e16
+    return {"sparse": sparse, "dense": dense}

@@ -280,3 +280,220 @@ def test_shrink_case_switches_from_full_step_to_replay():
     assert abs(attempts[0]["rho"] - 1.416412642) < 1e-8
     assert abs(attempts[-1]["rho"] - 1.286575622) < 1e-8
     assert attempts[-1]["radius"] == 1562.5
+
+
+# ------------------------------------------- certificate kernel matrix
+# Every bound of the certificate matrix is checked twice here: the fp64
+# reference lies within HALF its bound of a numpy.longdouble evaluation
+# of the same operation (the device gets the other half), and the
+# bound's maximum is below 1e-3 of the median magnitude of what it
+# guards, so a dropped term or a wrong Lambda entry cannot hide.
+LD = np.longdouble
+
+
+def _ld(t):
+    return t.numpy().astype(LD)
+
+
+def _within_half(ref, exact, bound, what):
+    err = np.abs(np.asarray(ref, dtype=np.float64).astype(LD) - exact)
+    half = 0.5 * np.asarray(bound, dtype=np.float64).astype(LD)
+    assert (err <= half).all(), (what, float(err.max()))
+
+
+def _sees_fault(bound, guarded, what):
+    b = float(np.max(np.asarray(bound, dtype=np.float64)))
+    med = float(np.median(np.abs(np.asarray(guarded, dtype=np.float64))))
+    assert 0.0 <= b < 1e-3 * med, (what, b, med)
+
+
+def _s_apply_ld(Q, lam, v):
+    """(Q - Lambda) v in longdouble on the scalar CSR (every row has its
+    diagonal block, so reduceat sees no empty row)."""
+    csr = Q.to_scalar_csr()
+    crow = csr.crow_indices().numpy()
+    assert (np.diff(crow) > 0).all()
+    prod = csr.values().numpy().astype(LD) * v[csr.col_indices().numpy()]
+    w = np.add.reduceat(prod, crow[:-1])
+    n, d = lam.shape[0], lam.shape[1]
+    wb = w.reshape(n, d + 1)
+    wb[:, :d] -= np.einsum("nab,nb->na", _ld(lam),
+                           v.reshape(n, d + 1)[:, :d])
+    return w
+
+
+def test_cert_sizes_reach_the_wrap():
+    assert np.finfo(LD).eps < 1e-18
+    for d, ns in kr.CERT_ROW_POSES.items():
+        N = [(d + 1) * n for n in ns]
+        assert cpu_ref.cert_partials(N[-1]) == 256
+        assert 0 < N[-1] - 65536 <= 4          # rows on a second trip
+    assert 4 * kr.CERT_ROW_POSES[3][-2] == 65536
+    assert kr.cert_lambda_poses(3, 8)[-1] == 65537
+    assert kr.cert_lambda_poses(2, 6)[-1] == 65537
+    assert kr.cert_lambda_poses(3, 5) == kr.N_POSE
+    assert kr.cert_steps_for(3) == (0, 1) and kr.cert_steps_for(4) == (0, 1)
+    assert kr.cert_steps_for(192) == kr.CERT_STEPS
+    Q, Qa = kr.cert_matrix(65, 3)
+    assert kr.cert_matrix(65, 3)[0] is Q
+    assert torch.equal(Qa.vals, Q.vals.abs())
+
+
+@pytest.mark.parametrize("d,r", kr.SHAPES)
+def test_cert_lambda_ref_and_bounds(d, r):
+    for n in kr.cert_lambda_poses(d, r):
+        g = kr.gen(41, d, r, n)
+        X = kr.manifold_point(n, d, r, g)
+        QX = kr.randn(g, (d + 1) * n, r)
+        lam, res, b_lam, b_res = kr.cert_lambda_ref(X, QX, d)
+        Xl = _ld(X).reshape(n, d + 1, r)
+        Gl = _ld(QX).reshape(n, d + 1, r)
+        A = np.einsum("nak,nbk->nab", Gl[:, :d], Xl[:, :d])
+        L = 0.5 * (A + A.transpose(0, 2, 1))
+        gl = Gl.copy()
+        gl[:, :d] -= np.einsum("nab,nbk->nak", L, Xl[:, :d])
+        _within_half(lam.numpy(), L, b_lam.numpy(), ("lam", d, r, n))
+        _within_half(res, (gl * gl).sum(), b_res, ("res", d, r, n))
+        _sees_fault(b_lam, lam, ("lam", d, r, n))
+        _sees_fault(b_res, res, ("res", d, r, n))
+    # with QX = Q X it is cpu_ref.cert_lambda
+    Q, _ = kr.cert_matrix(65, d)
+    X = kr.manifold_point(65, d, r, kr.gen(47, d, r))
+    lam_c, res_c = cpu_ref.cert_lambda(Q, X, d)
+    lam, res, b_lam, b_res = kr.cert_lambda_ref(X, Q.spmm(X), d)
+    assert bool(((lam - lam_c).abs() <= b_lam).all())
+    assert abs(res - float(res_c)) <= b_res
+
+
+@pytest.mark.parametrize("d,n", [(2, 1), (2, 65), (2, 21846), (3, 1),
+                                 (3, 64), (3, 65), (3, 16385)])
+def test_cert_apply_ref_and_bounds(d, n):
+    N = n * (d + 1)
+    Q, Qa = kr.cert_matrix(n, d)
+    g = kr.gen(42, d, n)
+    lam = kr.cert_lam_blocks(n, d, g)
+    v, vprev = kr.randn(g, N), kr.randn(g, N)
+    for vp, beta in ((None, 0.0), (vprev, kr.CERT_BETA_PREV)):
+        w, alpha, b_w, b_a = kr.cert_apply_ref(Q, Qa, lam, v, vp, beta)
+        wl = _s_apply_ld(Q, lam, _ld(v))
+        if vp is not None:
+            wl -= LD(beta) * _ld(vp)
+        _within_half(w.numpy(), wl, b_w.numpy(), ("w", d, n))
+        _within_half(alpha, np.dot(_ld(v), wl), b_a, ("alpha", d, n))
+        _sees_fault(b_w, w, ("w", d, n))
+        _sees_fault(b_a, alpha, ("alpha", d, n))
+    assert kr.cert_apply_terms(Q, d) == \
+        int(np.diff(Q.row_ptr.numpy()).max()) * (d + 1) + d + 1
+
+
+@pytest.mark.parametrize("d,n", [(2, 1), (2, 65), (2, 21846), (3, 1),
+                                 (3, 64), (3, 65), (3, 16385)])
+def test_cert_step_ref_and_bounds(d, n):
+    """cert_step_ref against a longdouble run of the same step, and
+    cpu_ref.cert_lanczos_steps (the reference of alpha, beta and v_{j+1}
+    on the device) against the same run under the same bounds."""
+    N = n * (d + 1)
+    M, H = kr.CERT_M, cpu_ref.CERT_HDR
+    for j in kr.cert_steps_for(N):
+        Q, Qa, lam, V, ctl = kr.cert_step_state(n, d, j)
+        assert bool((V[j + 1:] == kr.CERT_SENTINEL).all())
+        G = V[:j + 1] @ V[:j + 1].T
+        assert float((G - torch.eye(j + 1, dtype=torch.float64)).abs()
+                     .max()) < 1e-13
+        st = kr.cert_step_ref(Q, Qa, lam, V, ctl, j)
+        Vc, cc = V.clone(), ctl.clone()
+        cpu_ref.cert_lanczos_steps(Q, lam, Vc, cc, j, 1)
+        assert float(cc[cpu_ref.CERT_COUNT]) == j + 1
+        assert bool((Vc[j + 2:] == kr.CERT_SENTINEL).all())
+        # the same step in longdouble
+        Bl = _ld(V[:j + 1])
+        wl = _s_apply_ld(Q, lam, Bl[j])
+        if j > 0:
+            wl -= LD(float(ctl[H + M + j - 1])) * Bl[j - 1]
+        what = (d, n, j)
+        _within_half(st.w0.numpy(), wl, st.b_w0.numpy(), ("w0",) + what)
+        al = np.dot(Bl[j], wl)
+        _within_half(st.alpha, al, st.b_alpha, ("alpha",) + what)
+        _within_half(float(cc[H + j]), al, st.b_alpha, ("alpha c",) + what)
+        for p in (1, 2):
+            cl = Bl @ wl
+            _within_half(getattr(st, f"c{p}").numpy(), cl,
+                         getattr(st, f"b_c{p}").numpy(), (f"c{p}",) + what)
+            wl = wl - Bl.T @ cl
+            _within_half(getattr(st, f"w{p}").numpy(), wl,
+                         getattr(st, f"b_w{p}").numpy(), (f"w{p}",) + what)
+        b2 = (wl * wl).sum()
+        bl = np.sqrt(b2)
+        _within_half(st.beta2, b2, st.b_beta2, ("beta2",) + what)
+        _within_half(st.beta, bl, st.b_beta, ("beta",) + what)
+        _within_half(float(cc[H + M + j]), bl, st.b_beta, ("beta c",) + what)
+        _within_half(st.vnext.numpy(), wl / bl, st.b_v.numpy(),
+                     ("v",) + what)
+        _within_half(Vc[j + 1].numpy(), wl / bl, st.b_v.numpy(),
+                     ("v c",) + what)
+        _sees_fault(st.b_w2, st.w2, ("w2",) + what)
+        _sees_fault(st.b_v, st.vnext, ("v",) + what)
+        _sees_fault(st.b_alpha, st.alpha, ("alpha",) + what)
+        _sees_fault(st.b_beta, st.beta, ("beta",) + what)
+        _sees_fault(st.b_beta2, st.beta2, ("beta2",) + what)
+        _sees_fault(st.b_c1, st.c1, ("c1",) + what)
+        # the second-pass coefficients are rounding noise themselves
+        # (about eps ||w||): what their bound must see is one dropped
+        # product of the Gram sum
+        assert float(st.c2.abs().max()) < 64 * N * kr.EPS * st.beta
+        terms = (V[:j + 1].abs() * st.w1.abs()[None, :])
+        _sees_fault(st.b_c2, terms, ("c2",) + what)
+
+
+@pytest.mark.parametrize("kind,tol,beta_prev", [
+    ("threshold", 1e300, kr.CERT_BETA_PREV), ("zero", 0.0, 0.0),
+    ("nan", 0.0, kr.CERT_BETA_PREV), ("flag", 0.0, kr.CERT_BETA_PREV)])
+def test_cert_breakdown_outcomes_of_the_cpu_reference(kind, tol, beta_prev):
+    """What the device tests expect of each k_cert_norm branch and of a
+    raised flag is what cpu_ref.cert_lanczos_steps does."""
+    d, n, j = 3, 65, 1
+    M, H = kr.CERT_M, cpu_ref.CERT_HDR
+    Q, _, lam, V, ctl = kr.cert_step_state(n, d, j, tol=tol,
+                                           beta_prev=beta_prev)
+    if kind == "zero":
+        Q, lam = kr.cert_zero_matrix(n, d), torch.zeros_like(lam)
+    elif kind == "nan":
+        V[j, V.shape[1] - 3] = float("nan")
+    elif kind == "flag":
+        ctl[cpu_ref.CERT_FLAG] = 1.0
+    Vc, cc = V.clone(), ctl.clone()
+    cpu_ref.cert_lanczos_steps(Q, lam, Vc, cc, j, 3)
+    assert bool((Vc[j + 1:] == kr.CERT_SENTINEL).all())
+    assert float(cc[cpu_ref.CERT_FLAG]) == 1.0
+    if kind == "flag":
+        assert torch.equal(cc, ctl)
+        return
+    assert float(cc[H + M + j]) == 0.0
+    assert float(cc[cpu_ref.CERT_COUNT]) == j + 1
+    assert float(cc[H + j + 1]) == float(ctl[H + j + 1])
+    assert float(cc[H + M + j + 1]) == float(ctl[H + M + j + 1])
+    assert math.isnan(float(cc[H + j])) == (kind == "nan")
+    if kind == "zero":
+        assert float(cc[H + j]) == 0.0
+
+
+def test_cert_fixed_order_sum_is_not_a_plain_sum():
+    cases = kr.cert_fanin_cases()
+    for p in cases.values():
+        assert p.shape == (256,)
+        assert (p[0], p[1], p[255]) == (1e16, 1.0, -1e16)
+    s = cases["sparse"]
+    assert math.fsum(s) == 1.0 and kr.cert_fixed_order_sum(s) == 0.0
+    assert kr.cert_fixed_order_sum(s[:255]) == 1e16     # a dropped slot
+    p = cases["dense"]
+    dev = kr.cert_fixed_order_sum(p)
+    naive = 0.0
+    for x in p.tolist():
+        naive += x
+    assert dev != math.fsum(p) and dev != naive
+    # another wave order is another number
+    assert dev != kr.cert_fixed_order_sum(p, (3, 2, 1, 0))
+    assert dev != kr.cert_fixed_order_sum(p[:255])
+    # exact on exactly representable data, and a short list is padded
+    q = np.arange(1.0, 201.0)
+    assert kr.cert_fixed_order_sum(q) == 200 * 201 / 2
